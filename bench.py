@@ -18,6 +18,11 @@ SURVEY.md §8d) + the 12-B descriptor, computed from the records the kernel wrot
 Multi-GPU: one process per GPU (torch.distributed, launched by torch.distributed.run); packets are
 independent, so each rank parses its own 10M-packet shard with no data-path collective ("weak").
 Rank 0 prints one JSON line. value = packets of all ranks / max-over-ranks time.
+
+A plain run sets up, warms up, times --steps steps and prints the line (value, ms_per_step, the kernel times).
+--dump-outputs DIR also writes the records the last timed step left (rank 0; a fixed, seeded sample) as DIR/<name>.npy.
+--full adds everything else: the untimed check parse (flagged packets, record cross-checks, roofline), the PMC traffic
+file, the host-to-host timing, config 4's flow-table merge and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -78,6 +83,16 @@ def parse_args():
                              f"config {c} {v}" for c, v in sorted(CONFIG_RECORDS.items())) + ")")
     ap.add_argument("--dump-flows", default=None,
                     help="config 4: write the merged flow table (rank 0, after the timed region) to this .npz")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the untimed check parse (flagged packets, record cross-checks, the "
+                         "roofline figures), the PMC traffic file, the host-to-host timing, config 4's flow-table merge "
+                         "and the CPU baseline (--no-traffic / --no-e2e / --no-cpu-baseline drop single ones). A plain "
+                         "run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step left in the timed launch's output arrays "
+                         f"(rank 0) as DIR/<name>.npy in float64: the records of a fixed, seeded sample of {DUMP_TILES} "
+                         "64-packet tiles (all packets of a smaller batch) as their 32-bit words, the layer rows in the "
+                         "FIXED form with the entries past a chain zero; config 4 also its flow table, sorted by key")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="gloo: a multi-rank rehearsal on fewer GPUs than ranks (ranks share cards round-robin); "
                          "the timed numbers of such a run are not a scaling measurement")
@@ -96,6 +111,8 @@ CONFIG_RECORDS = {2: "tuples", 3: "brief", 4: "keys", 5: "brief"}
 # plain Eth / VLAN / IP / L4 stacks (configs 2 and 4): the one-round parse-only window (PCPPX_WINDOW_SHORT)
 CONFIG_WINDOW = {2: "short", 4: "short"}
 KERNEL_SRC = ROOT / "pcapplusplus_amd" / "csrc" / "pcppx_kernels.hip"
+DUMP_TILES = 2048  # --dump-outputs: 64-packet tiles in the sample (131072 packets: 4 MB of briefs, 17-25 MB of layer rows)
+DUMP_SEED = 0
 
 
 def kernel_sha() -> str:
@@ -190,6 +207,76 @@ def cpu_baseline(batch, opts, sample: int, min_seconds: float) -> dict:
                       f"{total_t:.1f} s; {'reference Packet++ built from source' if kind == 'reference' else 'C restatement'}"
                       f": Packet(&raw) + hash5Tuple x2 + hash2Tuple"
                       f"{' + IPv4/L4 checksums' if opts.want_checksums else ''}, {threads} threads = {core_note}"}
+
+
+def dump_outputs(out_dir: Path, dev: str, n: int, ml: int, layout: str, summary, brief, tuples, layers, flow_keys,
+                 flows, proto_stats) -> dict:
+    """--dump-outputs: the timed launch's output arrays as the last step left them, as float64 .npy files (every value
+    a 32-bit word or a counter below 2^53, so exact). Per-packet records are those of a fixed sample of whole 64-packet
+    tiles (`packets`: their indices), as rows of little-endian 32-bit words; the layer rows are decoded to the FIXED
+    [packet, max_layers] form with the entries past a chain zero (the launch leaves those bytes unwritten), two words
+    per entry. Config 4's flow table holds every launch's counts (warmup + steps), its used slots sorted by key (a slot's
+    place in the table depends on the order the atomics landed in). Returns {name: shape}."""
+    import torch
+
+    from pcapplusplus_amd import abi, shard
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    tiles = -(-n // abi.TILE)
+    if tiles > DUMP_TILES:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n // abi.TILE, DUMP_TILES, replace=False))
+    else:
+        pick = np.arange(tiles)
+    idx = (pick[:, None] * abi.TILE + np.arange(abi.TILE)[None, :]).ravel()
+    idx = idx[idx < n]
+    didx = torch.from_numpy(idx).to(dev)
+    written = {}
+
+    def save(name, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(out_dir / f"{name}.npy", a)
+        written[name] = list(a.shape)
+
+    def words(t, nbytes):
+        return t.view(torch.int32).view(n, nbytes // 4)[didx].cpu().numpy().view(np.uint32)
+
+    save("packets", idx)
+    recs = None
+    if summary is not None:
+        w = words(summary, 32)
+        recs = w.view(abi.SUMMARY_DTYPE).ravel()
+        save("summary", w)
+    if brief is not None:
+        w = words(brief, 16)
+        recs = w.view(abi.BRIEF_DTYPE).ravel()
+        save("brief", w)
+    if tuples is not None:
+        w = words(tuples, 48)
+        w[:, 11] &= 0x00FFFFFF  # pcppx_tuple's reserved byte
+        save("tuples", w)
+    if flow_keys is not None:
+        save("flow_keys", flow_keys[didx].cpu().numpy().view(np.uint32))
+    if ml and recs is not None:
+        ent = layers.view(torch.int64)  # one 8-B layer entry each
+        if layout == "packed":  # a tile's chains sit back to back from its base 64 * tile * max_layers
+            e = (pick[:, None] * (abi.TILE * ml) + np.arange(abi.TILE * ml)[None, :]).ravel()
+            e = e[e < n * ml]
+            raw = ent[torch.from_numpy(e).to(dev)].cpu().numpy().view(abi.LAYER_DTYPE)
+            rows = abi.unpack_layers(recs, raw, ml)
+        else:
+            rows = ent[: n * ml].view(n, ml)[didx].cpu().numpy().view(abi.LAYER_DTYPE)
+            past = np.arange(ml)[None, :] >= np.minimum(recs["n_layers"], ml)[:, None]
+            rows.view(np.int64)[past] = 0
+        save("layers", rows.view(np.uint32).reshape(len(recs), 2 * ml))
+    if flows is not None:
+        keys, pk, by, st, _ = flows
+        t = shard.compact_device_table(keys.cpu().numpy(), pk.cpu().numpy(), by.cpu().numpy(), st.cpu().numpy())
+        o = np.argsort(t["keys"], kind="stable")
+        save("flow_table", np.stack([t["keys"][o].astype(np.uint64), t["packets"][o], t["bytes"][o]], axis=1))
+        save("flow_table_stats", t["stats"])
+    if proto_stats is not None:
+        save("proto_stats", proto_stats.cpu().numpy())
+    return written
 
 
 def free_port() -> int:
@@ -367,75 +454,78 @@ def main() -> None:
     total_packets = n * world * args.steps
     mpps = total_packets / wall_max / 1e6
     wire = int(batch.caplens.sum(dtype=np.int64))
-    # the records' chain lengths (packed write bytes), the flag check and -- for parse-only runs -- the header extents
-    # (their byte model): from the timed run's own summary when it has one and computes checksums; else from one
-    # untimed parse with full FIXED records through the checksum instance (the same records; for a checksum run that
-    # writes no summary -- configs 3 with the brief -- the same kernel, launched once after the timed region:
-    # tools/timed_stats.py keeps launches warmup+1 .. warmup+steps)
-    if want_csum and summary is not None:
-        ext_sum = summary
-        read_bytes = algorithmic_read_bytes(batch, True)
-    else:
-        ext_sum = torch.empty(n * 32, dtype=torch.uint8, device=dev)
-        ext_lay = torch.empty(n * 16 * 8, dtype=torch.uint8, device=dev)
-        eng.parse_device(data, offsets, caplens, n, batch.linktype, abi.make_opts(0, 8, True, 16), ext_sum, ext_lay, sh)
-        torch.cuda.synchronize(dev)
-        read_bytes = algorithmic_read_bytes(batch, want_csum, ext_sum, ext_lay, caplens, 16)
-        del ext_lay
-    nl16 = ext_sum.view(n, 32)[:, 14].to(torch.int64)
-    chain_entries = int(torch.clamp(nl16, max=ml).sum().item()) if ml else 0
-    per_pkt = (32 if summary is not None else 0) + (16 if brief is not None else 0) + \
-        (48 if tuples is not None else 0) + (4 if flow_keys is not None else 0)
-    write_bytes = n * per_pkt + {"fixed": 8 * n * ml, "packed": 8 * chain_entries}[layout]
-    achieved = read_bytes / (kern_ms * 1e-3) / 1e9
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs: the arrays as the last timed step left them
+        dumped = dump_outputs(Path(args.dump_outputs), dev, n, ml, layout, summary, brief, tuples, layers, flow_keys,
+                              flows, proto_stats)
+    read_bytes = write_bytes = achieved = flagged = tuple_check = keys_equal = brief_equal = stats_line = None
+    if args.full:
+        # the records' chain lengths (packed write bytes), the flag check and -- for parse-only runs -- the header
+        # extents (their byte model): from the timed run's own summary when it has one and computes checksums; else
+        # from one untimed parse with full FIXED records through the checksum instance (the same records; for a
+        # checksum run that writes no summary -- configs 3 with the brief -- the same kernel, launched once after the
+        # timed region: tools/timed_stats.py keeps launches warmup+1 .. warmup+steps)
+        if want_csum and summary is not None:
+            ext_sum = summary
+            read_bytes = algorithmic_read_bytes(batch, True)
+        else:
+            ext_sum = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+            ext_lay = torch.empty(n * 16 * 8, dtype=torch.uint8, device=dev)
+            eng.parse_device(data, offsets, caplens, n, batch.linktype, abi.make_opts(0, 8, True, 16), ext_sum, ext_lay,
+                             sh)
+            torch.cuda.synchronize(dev)
+            read_bytes = algorithmic_read_bytes(batch, want_csum, ext_sum, ext_lay, caplens, 16)
+            del ext_lay
+        nl16 = ext_sum.view(n, 32)[:, 14].to(torch.int64)
+        chain_entries = int(torch.clamp(nl16, max=ml).sum().item()) if ml else 0
+        per_pkt = (32 if summary is not None else 0) + (16 if brief is not None else 0) + \
+            (48 if tuples is not None else 0) + (4 if flow_keys is not None else 0)
+        write_bytes = n * per_pkt + {"fixed": 8 * n * ml, "packed": 8 * chain_entries}[layout]
+        achieved = read_bytes / (kern_ms * 1e-3) / 1e9
 
-    # sanity: every packet parses cleanly (synthetic data has no L7 triggers)
-    s = ext_sum.view(torch.int32).view(n, 8)
-    flags = (s[:, 3] & 0xFFFF)
-    flagged = int(((flags & abi.F_NEEDS_HOST) != 0).sum().item())
-    if tuples is not None:  # the timed output itself: every packet carries its 5-tuple, hash5 as the summary's
-        tv = tuples.view(torch.int32).view(n, 12)
-        tuple_check = {"with_5tuple": int(((tv[:, 9] >> 24) & 0xFF).eq(1).sum().item()),
-                       "hash5_equal_summary": bool(torch.equal(tv[:, 10], s[:, 0]))}
-    else:
-        tuple_check = None
-    # the flow table's keys: the timed launches' dense hash5 column equals the full parse's summary hash5
-    keys_equal = bool(torch.equal(flow_keys, s[:, 0])) if flow_keys is not None else None
-    # the timed launches' briefs: the first half of the full parse's summaries, byte for byte (a parse-only run against
-    # the checksum parse above: but for its checksum flags)
-    brief_equal = None
-    if brief is not None:
-        want16 = ext_sum.view(n, 32)[:, :16].clone()
-        if not want_csum:
-            csum_flags = abi.F_IP_CSUM | abi.F_IP_CSUM_OK | abi.F_L4_CSUM | abi.F_L4_CSUM_OK
-            w = want16.view(torch.int32)
-            w[:, 3] &= ~csum_flags
-        brief_equal = bool(torch.equal(brief.view(n, 16), want16))
-    stats_line = None
-    if proto_stats is not None:  # collectStats over every launch (warmup + timed): the histogram of one pass
-        launches = args.warmup + args.steps
-        tot = proto_stats.cpu().numpy()
-        consistent = bool((tot % launches == 0).all() and int(tot[0]) // launches == n)
-        if world > 1:
-            # every rank's PacketStats summed, as FilterTraffic sums its per-core stats at exit
-            # (Examples/DpdkExample-FilterTraffic/main.cpp:279-287); after the timed region
-            tt = torch.tensor(np.concatenate([tot, [1 if consistent else 0]]).astype(np.int64), device=tdev)
-            dist.all_reduce(tt, op=dist.ReduceOp.SUM)
-            tot, consistent = tt[:-1].cpu().numpy(), int(tt[-1]) == world
-        stats_line = {f: int(tot[k]) // launches for k, f in enumerate(abi.PROTO_STATS_FIELDS)}
-        stats_line["launches_per_rank"] = launches
-        stats_line["ranks_merged"] = world
-        stats_line["consistent"] = consistent and stats_line["packet_count"] == n * world
-    del ext_sum
+        # sanity: every packet parses cleanly (synthetic data has no L7 triggers)
+        s = ext_sum.view(torch.int32).view(n, 8)
+        flags = (s[:, 3] & 0xFFFF)
+        flagged = int(((flags & abi.F_NEEDS_HOST) != 0).sum().item())
+        if tuples is not None:  # the timed output itself: every packet carries its 5-tuple, hash5 as the summary's
+            tv = tuples.view(torch.int32).view(n, 12)
+            tuple_check = {"with_5tuple": int(((tv[:, 9] >> 24) & 0xFF).eq(1).sum().item()),
+                           "hash5_equal_summary": bool(torch.equal(tv[:, 10], s[:, 0]))}
+        # the flow table's keys: the timed launches' dense hash5 column equals the full parse's summary hash5
+        keys_equal = bool(torch.equal(flow_keys, s[:, 0])) if flow_keys is not None else None
+        # the timed launches' briefs: the first half of the full parse's summaries, byte for byte (a parse-only run
+        # against the checksum parse above: but for its checksum flags)
+        if brief is not None:
+            want16 = ext_sum.view(n, 32)[:, :16].clone()
+            if not want_csum:
+                csum_flags = abi.F_IP_CSUM | abi.F_IP_CSUM_OK | abi.F_L4_CSUM | abi.F_L4_CSUM_OK
+                w = want16.view(torch.int32)
+                w[:, 3] &= ~csum_flags
+            brief_equal = bool(torch.equal(brief.view(n, 16), want16))
+        if proto_stats is not None:  # collectStats over every launch (warmup + timed): the histogram of one pass
+            launches = args.warmup + args.steps
+            tot = proto_stats.cpu().numpy()
+            consistent = bool((tot % launches == 0).all() and int(tot[0]) // launches == n)
+            if world > 1:
+                # every rank's PacketStats summed, as FilterTraffic sums its per-core stats at exit
+                # (Examples/DpdkExample-FilterTraffic/main.cpp:279-287); after the timed region
+                tt = torch.tensor(np.concatenate([tot, [1 if consistent else 0]]).astype(np.int64), device=tdev)
+                dist.all_reduce(tt, op=dist.ReduceOp.SUM)
+                tot, consistent = tt[:-1].cpu().numpy(), int(tt[-1]) == world
+            stats_line = {f: int(tot[k]) // launches for k, f in enumerate(abi.PROTO_STATS_FIELDS)}
+            stats_line["launches_per_rank"] = launches
+            stats_line["ranks_merged"] = world
+            stats_line["consistent"] = consistent and stats_line["packet_count"] == n * world
+        del ext_sum
 
     traffic, traffic_note = None, "not requested"
-    if not args.no_traffic:
+    if args.full and not args.no_traffic:
         tag = f"{cfg}s{sized}" if sized else f"{cfg}"
         tp = Path(args.traffic) if args.traffic else ROOT / "profiles" / f"traffic_cfg{tag}.json"
         traffic, traffic_note = load_traffic(tp, cfg, n, ml, want_csum, layout, rec_kind, window, args.sizes)
 
     e2e = None
-    if not args.no_e2e and rank == 0 and world == 1:
+    if args.full and not args.no_e2e and rank == 0 and world == 1:
         # packets start and end in host memory: pcppx_parse_batch_host on the first 2M packets. pageable: input and
         # records in ordinary memory (staged / drained by host threads); pinned: input in page-locked memory (a NIC
         # ring: DMA from the caller's bytes); pinned_io: records returned into page-locked arrays too. Output arrays
@@ -468,7 +558,7 @@ def main() -> None:
                 k.free()
 
     flow_check = None
-    if flows is not None:
+    if flows is not None and (args.full or args.dump_flows):
         # FilterTraffic's exit step (Examples/DpdkExample-FilterTraffic/main.cpp:279-287): every GPU's flow table is
         # merged by key on the host (after the timed region; nothing crosses GPUs on the data path). Conservation:
         # every packet of every launch on every rank is in a flow, the key-0 bucket or the no-free-slot count.
@@ -501,7 +591,7 @@ def main() -> None:
                       f"not the reference's", file=sys.stderr, flush=True)
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:  # after the timed region (every rank's), so N>1 lines carry it too
+    if args.full and rank == 0 and not args.no_cpu_baseline:  # after the timed region (every rank's), so N>1 lines carry it too
         cpu = cpu_baseline(batch, opts, args.cpu_sample, args.cpu_seconds)
 
     if rank == 0:
@@ -542,10 +632,15 @@ def main() -> None:
                 "kernel_ms_min": round(float(np.min(kern_each)), 4),
                 "kernel_ms_max": round(float(np.max(kern_each)), 4),
                 "step_kernel_ms": round(step_ms, 4),
-                "flagged_packets": flagged,
                 "gen_seconds": round(gen_s, 1),
             },
-            "roofline": {
+            "full": args.full,
+        }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if args.full:
+            line["config"]["flagged_packets"] = flagged
+            line["roofline"] = {
                 "bound": "hbm",
                 "achieved": round(achieved, 1),
                 "peak": HBM_PEAK_GBPS,
@@ -559,9 +654,8 @@ def main() -> None:
                 # kernel's total algorithmic traffic against the same peak; `frac` above is the read side alone)
                 "rw_achieved": round((read_bytes + write_bytes) / (kern_ms * 1e-3) / 1e9, 1),
                 "rw_frac": round((read_bytes + write_bytes) / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-            },
-            "cpu_baseline": cpu,
-        }
+            }
+            line["cpu_baseline"] = cpu
         if e2e is not None:
             line["e2e_host_to_host"] = e2e
         if flow_check is not None:

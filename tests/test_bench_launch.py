@@ -88,7 +88,7 @@ def test_bench_small_run_checks_its_records(cfg):
     import json
 
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", str(cfg), "--packets", "200000", "--steps",
-                        "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-traffic"],
+                        "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e", "--no-traffic"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -120,7 +120,7 @@ def test_bench_ranks_self_launch(ranks, cfg, tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     dump = tmp_path / "flows.npz"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(ranks), "--dist-backend", "gloo",
-                        "--config", str(cfg), "--packets", str(npk), "--steps", "3", "--warmup", "1", "--no-e2e",
+                        "--config", str(cfg), "--packets", str(npk), "--steps", "3", "--warmup", "1", "--full", "--no-e2e",
                         "--no-traffic", "--cpu-sample", "20000", "--cpu-seconds", "0.5", "--dump-flows", str(dump)],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -157,3 +157,44 @@ def test_bench_ranks_self_launch(ranks, cfg, tmp_path):
         if m["key0"][0]:
             got[-1] = (int(m["key0"][0]) // launches, int(m["key0"][1]) // launches)
         assert got == want and int(m["key0"][2]) == 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_timed_outputs(tmp_path):
+    """A plain run (no --full) times its steps and prints the headline figures without the check parse, the roofline or
+    the CPU baseline; --dump-outputs writes the timed launch's own arrays (config 3: the 16-B briefs and the PACKED
+    layer rows, decoded) for a seeded sample of whole 64-packet tiles as float64 .npy, and they are the restatement's
+    records of those packets of the same seeded batch, word for word."""
+    import json
+
+    import numpy as np
+
+    import oracle
+    from pcapplusplus_amd import abi, shard, synth
+
+    npk, out = 200_000, tmp_path / "out"  # 3125 tiles: more than the sample, so the sampled path runs
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--packets", str(npk), "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["full"] is False and line["steps"] == 2 and line["unit"] == "Mpackets/s" and line["dtype"] == "u8"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert abs(line["value"] - npk / line["ms_per_step"] / 1e3) <= 0.01 * line["value"]
+    assert not {"roofline", "cpu_baseline", "e2e_host_to_host"} & set(line)
+    assert "flagged_packets" not in line["config"] and "brief_equal_summary_half" not in line["config"]
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(files) == set(line["dumped_outputs"]) == {"packets", "brief", "layers"}
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    idx = files["packets"].astype(np.int64)
+    assert len(idx) == bench.DUMP_TILES * abi.TILE and (np.diff(idx) > 0).all() and idx[-1] < npk
+    assert (idx.reshape(-1, abi.TILE) == idx[::abi.TILE, None] + np.arange(abi.TILE)).all() and not (idx[::64] % 64).any()
+    b = synth.imix(npk, shard.shard_seed(3, 0))
+    s, lay = oracle.oracle_parse(b, abi.make_opts(0, 8, True, 8), threads=8)
+    assert files["brief"].shape == (len(idx), 4) and files["layers"].shape == (len(idx), 16)
+    want = s[idx].view(np.uint32).reshape(len(idx), 8)[:, :4]
+    assert (files["brief"] == want).all()
+    past = np.arange(8)[None, :] >= np.minimum(s["n_layers"][idx], 8)[:, None]
+    rows = lay[idx].copy()
+    rows[past] = np.zeros(1, abi.LAYER_DTYPE)
+    assert (files["layers"] == rows.view(np.uint32).reshape(len(idx), 16)).all()

@@ -55,14 +55,14 @@ for step in "$@"; do
       grep -E "^map|^copy|^config1|^example|^imix|^filter|^google|^first_pass" "$OUT/${TAG}_e2e.log" | cut -c1-500 ;;
     bench)
       for c in ${arg//,/ }; do
-        timeout -k 10 400 python -u bench.py $(cfgargs "$c") $(tr "$c") > "$OUT/${TAG}_bench_cfg$c.json" \
+        timeout -k 10 400 python -u bench.py --full $(cfgargs "$c") $(tr "$c") > "$OUT/${TAG}_bench_cfg$c.json" \
           2> "$OUT/${TAG}_bench_cfg$c.err" || { tail -20 "$OUT/${TAG}_bench_cfg$c.err"; exit 4; }
         echo "cfg $c: $(head -c 400 "$OUT/${TAG}_bench_cfg$c.json")"
       done ;;
     prof)
       for c in ${arg//,/ }; do
         (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/${TAG}_prof_cfg$c" \
-          -o bench --output-format csv -- python3 "$ROOT/bench.py" $(cfgargs "$c") --steps 100 --warmup 5 --no-e2e $(tr "$c") \
+          -o bench --output-format csv -- python3 "$ROOT/bench.py" --full $(cfgargs "$c") --steps 100 --warmup 5 --no-e2e $(tr "$c") \
           > "$ROOT/$OUT/${TAG}_prof_bench_cfg$c.json" 2> "$ROOT/$OUT/${TAG}_prof_cfg$c.err") \
           || { tail -20 "$OUT/${TAG}_prof_cfg$c.err"; exit 5; }
         python3 tools/timed_stats.py "$OUT/${TAG}_prof_cfg$c" "$OUT/${TAG}_prof_bench_cfg$c.json" \
