@@ -401,6 +401,62 @@ PCPPX_API int pcppx_reasm_device(pcppx_ctx* ctx, const pcppx_batch* batch, const
 PCPPX_API int pcppx_parse_batch_device_reasm(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_opts* opts,
                                    pcppx_records* out, pcppx_reasm_info* info, void* hip_stream);
 
+/* ---- select: gather the kept packets of a device batch into a packed batch (the worker's send-on step) ----
+ * What FilterTraffic's worker does after isMatched (sendPacketsTo->sendPacket / pcapWriter->writePacket,
+ * AppWorkerThread.h:127-139), for packets that sit in HBM: a stable stream compaction of variable-length packets.
+ * The packets chosen by a mask (pcppx_filter_device's matched[]) or by a flags test (a parse's summary / brief flags,
+ * e.g. PCPPX_F_NEEDS_HOST: the packets the host must finish) are copied, in source order, back to back into
+ * out->data, with offsets / caplens (an ordinary pcppx_batch for every other entry point) and their source packet
+ * numbers. Added within ABI 7: new symbols only, no existing record or call changes (PCPPX_ABI_VERSION stays 7). */
+typedef struct pcppx_select_spec {
+	const uint8_t* keep;   /* device, n bytes: packet i is selected iff keep[i] != 0. NULL = flags mode */
+	const void* flags;     /* flags mode: device address of packet 0's 16-bit flags word
+	                          (&summary[0].flags or &brief[0].flags) */
+	uint32_t flags_stride; /* bytes between consecutive packets' flags words (32 summary / 16 brief) */
+	uint16_t flags_any;    /* flags mode: selected iff (flags & flags_any) != 0 */
+	uint8_t invert;        /* 1: select the complement (the unmatched stream) */
+	uint8_t reserved;
+	uint32_t snaplen;      /* 0 = whole packet; else the output caplen is min(caplen, snaplen) */
+	uint32_t reserved2;
+} pcppx_select_spec;
+
+/* pcppx_selection.totals words */
+#define PCPPX_SEL_SELECTED_PACKETS 0 /* packets the rule chose whose descriptor is in bounds */
+#define PCPPX_SEL_SELECTED_BYTES 1   /* their output lengths (after snaplen) */
+#define PCPPX_SEL_WRITTEN_PACKETS 2  /* the prefix of them that fitted max_packets / data_cap */
+#define PCPPX_SEL_WRITTEN_BYTES 3
+#define PCPPX_SEL_BAD_DESC 4         /* packets the rule chose with offsets[i] + caplens[i] > data_len: never read,
+                                        never selected */
+#define PCPPX_SEL_TOTALS 8           /* words 5-7 zero */
+
+typedef struct pcppx_selection { /* all device pointers */
+	uint8_t* data;        /* packed bytes of the written packets, back to back, no padding; NULL = index-only */
+	uint64_t data_cap;
+	uint64_t* offsets;    /* max_packets entries: offsets[j] = sum of the output lengths of selected packets < j */
+	uint32_t* caplens;    /* max_packets entries */
+	uint32_t* index;      /* optional (NULL): index[j] = source packet number, strictly ascending */
+	uint32_t max_packets;
+	uint32_t reserved;
+	uint64_t* totals;     /* PCPPX_SEL_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_selection;
+
+/* Written rule: the selected packet of rank r (source order) at exclusive byte position p is written iff
+ * r < max_packets and, when data != NULL, p + len <= data_cap. Both conditions are monotone, so the written packets
+ * are a prefix of the selected ones; no packet is written partially. Entries offsets / caplens / index[j] for
+ * j >= WRITTEN_PACKETS and bytes of data at or beyond WRITTEN_BYTES are not touched. With data == NULL (index-only)
+ * no bytes move, the byte capacity is not applied and offsets hold the would-be positions. A packet of any caplen
+ * (0, or above PCPPX_MAX_CAPLEN) is copied: select is not a parse; the source batch may be gapped, unordered or
+ * overlapping; out->data must not overlap batch->data. Source bytes are read only through aligned 16-B granules
+ * (which never cross a page) that hold at least one byte of a selected, in-bounds packet.
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, spec, out, totals, offsets or caplens; keep and flags both
+ * null or both set; flags mode with a flags_stride other than 16 or 32; a non-zero reserved field. n == 0 is legal
+ * and writes zero totals. The work is queued on hip_stream and the call returns without waiting (the totals stay on
+ * the device); calls on one context are ordered (they share its scratch), as the flow-count calls are. */
+PCPPX_API int pcppx_select_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_select_spec* spec,
+                                  pcppx_selection* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_select_reference(const pcppx_batch* batch, const pcppx_select_spec* spec, pcppx_selection* out);
+
 /* ---- host ingest: pcap / pcapng captures into packed batch buffers ---- */
 typedef struct pcppx_pcap pcppx_pcap;
 /* Open a capture; the format comes from its first 4 bytes as IFileReaderDevice::createReader

@@ -146,6 +146,43 @@ class PacketStats(C.Structure):
         return {f: int(getattr(self, f)) for f in STATS_FIELDS}
 
 
+# pcppx_selection.totals words (PCPPX_SEL_*)
+SEL_SELECTED_PACKETS, SEL_SELECTED_BYTES, SEL_WRITTEN_PACKETS, SEL_WRITTEN_BYTES, SEL_BAD_DESC = 0, 1, 2, 3, 4
+SEL_TOTALS = 8
+SEL_FIELDS = ("selected_packets", "selected_bytes", "written_packets", "written_bytes", "bad_desc")
+FLAGS_OFFSET = SUMMARY_DTYPE.fields["flags"][1]  # the flags word's byte offset in a summary and in a brief
+assert FLAGS_OFFSET == BRIEF_DTYPE.fields["flags"][1] == 12
+
+
+class SelectSpec(C.Structure):
+    """pcppx_select_spec: which packets pcppx_select_device gathers (a keep mask, or a test of the parse's flags)."""
+    _fields_ = [("keep", C.c_void_p), ("flags", C.c_void_p), ("flags_stride", C.c_uint32), ("flags_any", C.c_uint16),
+                ("invert", C.c_uint8), ("reserved", C.c_uint8), ("snaplen", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+class Selection(C.Structure):
+    """pcppx_selection: the packed output batch, the source index and the totals."""
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("offsets", C.c_void_p), ("caplens", C.c_void_p),
+                ("index", C.c_void_p), ("max_packets", C.c_uint32), ("reserved", C.c_uint32), ("totals", C.c_void_p)]
+
+
+def make_select_spec(keep=None, flags=None, flags_stride: int = 0, flags_any: int = 0, invert: bool = False,
+                     snaplen: int = 0) -> SelectSpec:
+    """keep: address of the n-byte mask, or flags: address of packet 0's 16-bit flags word (records + FLAGS_OFFSET)
+    with flags_stride 32 (summary) / 16 (brief)."""
+    return SelectSpec(keep, flags, flags_stride, flags_any, 1 if invert else 0, 0, snaplen, 0)
+
+
+def totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(SEL_FIELDS)}
+
+
+def select_reference(batch: Batch, spec: SelectSpec, out: Selection) -> None:
+    """pcppx_select_reference: pcppx_select_device's contract in plain C++ over host pointers (no GPU). The structs
+    hold addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_select_reference(C.byref(batch), C.byref(spec), C.byref(out)), "pcppx_select_reference")
+
+
 def ipv4_to_int(dotted: str) -> int:
     """IPv4Address::toInt(): the address bytes in memory order read as a little-endian u32."""
     b = bytes(int(x) for x in dotted.split("."))
@@ -285,6 +322,10 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_window_choice.restype = C.c_int
     lib.pcppx_unpack_layers_brief.argtypes = [P, P, C.c_uint64, C.c_uint32, P]
     lib.pcppx_unpack_layers_brief.restype = C.c_int
+    lib.pcppx_select_device.argtypes = [P, C.POINTER(Batch), C.POINTER(SelectSpec), C.POINTER(Selection), P]
+    lib.pcppx_select_device.restype = C.c_int
+    lib.pcppx_select_reference.argtypes = [C.POINTER(Batch), C.POINTER(SelectSpec), C.POINTER(Selection)]
+    lib.pcppx_select_reference.restype = C.c_int
     for name in ("pcppx_device_count", "pcppx_open", "pcppx_sync", "pcppx_parse_batch_device",
                  "pcppx_parse_batch_host", "pcppx_flow_count_device"):
         getattr(lib, name).restype = C.c_int
@@ -300,6 +341,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_flow_count_device", "pcppx_flow_count_keys_device", "pcppx_filter_device", "pcppx_filter_reset", "pcppx_filter_batch_host", "pcppx_reasm_device", "pcppx_parse_batch_device_reasm", "pcppx_pcap_open", "pcppx_pcap_linktype",
     "pcppx_pcap_read_batch", "pcppx_pcap_read_batch_ex", "pcppx_pcap_map_batch", "pcppx_pcap_close", "pcppx_host_alloc", "pcppx_host_free",
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
+    "pcppx_select_device", "pcppx_select_reference",
 )
 
 

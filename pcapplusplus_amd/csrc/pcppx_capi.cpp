@@ -180,6 +180,11 @@ struct pcppx_ctx
 	uint64_t wave_stats_bytes = 0;
 	hipEvent_t stats_done = nullptr;
 	bool stats_pending = false;
+	// pcppx_select_device: the per-block sums and bases (28 B per 256 packets), ordered across calls like the flow scratch
+	void* d_select = nullptr;
+	uint64_t select_bytes = 0;
+	hipEvent_t select_done = nullptr;
+	bool select_pending = false;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -870,6 +875,10 @@ extern "C"
 			(void)hipFreeAsync(c->d_flow_fill, c->stream);
 		if (c->d_wave_stats)
 			(void)hipFreeAsync(c->d_wave_stats, c->stream);
+		if (c->select_pending)
+			(void)hipEventSynchronize(c->select_done);
+		if (c->d_select)
+			(void)hipFreeAsync(c->d_select, c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -884,6 +893,8 @@ extern "C"
 			(void)hipEventDestroy(c->flow_done);
 		if (c->stats_done)
 			(void)hipEventDestroy(c->stats_done);
+		if (c->select_done)
+			(void)hipEventDestroy(c->select_done);
 		(void)hipStreamDestroy(c->stream);
 		delete c;
 	}
@@ -1181,5 +1192,102 @@ extern "C"
 		if (brief == nullptr)
 			return PCPPX_E_INVAL;
 		return unpack_packed(&brief->n_layers, sizeof(pcppx_brief), packed, n, max_layers, fixed);
+	}
+}
+
+namespace
+{
+// the argument rules pcppx_select_device and pcppx_select_reference share (include/pcppx.h)
+bool valid_select(const pcppx_batch* b, const pcppx_select_spec* s, const pcppx_selection* o)
+{
+	if (b == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
+	    o->caplens == nullptr)
+		return false;
+	if ((s->keep == nullptr) == (s->flags == nullptr))
+		return false;
+	if (s->flags != nullptr && s->flags_stride != sizeof(pcppx_brief) && s->flags_stride != sizeof(pcppx_summary))
+		return false;
+	if (s->invert > 1 || s->reserved != 0 || s->reserved2 != 0 || o->reserved != 0)
+		return false;
+	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_select_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_select_spec* s, pcppx_selection* o,
+	                        void* hip_stream)
+	{
+		if (c == nullptr || !valid_select(b, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_SEL_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous select (possibly queued on another stream) owns the block sums until select_done
+		int rc = ensure_scratch(st, &c->d_select, &c->select_bytes, pcppx::select_scratch_bytes(b->n), &c->select_done,
+		                        c->select_pending);
+		if (rc != PCPPX_OK)
+			return rc;
+		rc = pcppx::launch_select(b, s, o, c->d_select, st);
+		if (rc != PCPPX_OK)
+			return rc;
+		if (!ok(hipEventRecord(c->select_done, st)))
+			return PCPPX_E_HIP;
+		c->select_pending = true;
+		return PCPPX_OK;
+	}
+
+	int pcppx_select_reference(const pcppx_batch* b, const pcppx_select_spec* s, pcppx_selection* o)
+	{
+		if (!valid_select(b, s, o))
+			return PCPPX_E_INVAL;
+		uint64_t sel = 0, sel_bytes = 0, written = 0, written_bytes = 0, bad = 0;
+		bool open = true;  // every selected packet so far was written
+		for (uint32_t i = 0; i < b->n; ++i)
+		{
+			bool chosen;
+			if (s->keep != nullptr)
+				chosen = s->keep[i] != 0;
+			else
+			{
+				uint16_t f;
+				std::memcpy(&f, static_cast<const uint8_t*>(s->flags) + (size_t)i * s->flags_stride, sizeof(f));
+				chosen = (f & s->flags_any) != 0;
+			}
+			if (chosen == (s->invert != 0))
+				continue;
+			const uint64_t off = b->offsets[i];
+			const uint32_t cap = b->caplens[i];
+			if (off + cap < off || off + cap > b->data_len)
+			{
+				++bad;
+				continue;
+			}
+			const uint32_t len = (s->snaplen != 0 && cap > s->snaplen) ? s->snaplen : cap;
+			open = open && sel < o->max_packets && (o->data == nullptr || sel_bytes + len <= o->data_cap);
+			if (open)
+			{
+				o->offsets[sel] = sel_bytes;
+				o->caplens[sel] = len;
+				if (o->index != nullptr)
+					o->index[sel] = i;
+				if (o->data != nullptr && len != 0)
+					std::memcpy(o->data + sel_bytes, b->data + off, len);
+				++written;
+				written_bytes += len;
+			}
+			++sel;
+			sel_bytes += len;
+		}
+		for (int k = 0; k < PCPPX_SEL_TOTALS; ++k)
+			o->totals[k] = 0;
+		o->totals[PCPPX_SEL_SELECTED_PACKETS] = sel;
+		o->totals[PCPPX_SEL_SELECTED_BYTES] = sel_bytes;
+		o->totals[PCPPX_SEL_WRITTEN_PACKETS] = written;
+		o->totals[PCPPX_SEL_WRITTEN_BYTES] = written_bytes;
+		o->totals[PCPPX_SEL_BAD_DESC] = bad;
+		return PCPPX_OK;
 	}
 }

@@ -37,4 +37,12 @@ int launch_dense_compact(const pcppx_layer* fixed, const uint8_t* n_layers, uint
 // chunks of a batch on the device: *cum_out = (*base_in or 0) + *count; at_base: entries at dst_mapped + base (else + 0)
 int launch_dense_push(const pcppx_layer* dense, const uint32_t* count, const uint32_t* base_in, pcppx_layer* dst_mapped,
                       bool at_base, uint32_t* cum_out, hipStream_t stream);
+// pcppx_select_device (pcppx_select.hip): count, block bases and copy, three launches on `stream`. scratch:
+// select_scratch_bytes(n) bytes of block sums and bases; one block gathers kSelectBlockPk packets (16 tiles).
+// Arguments are checked by the caller; n > 0.
+constexpr uint32_t kSelectBlockPk = 1024;
+uint32_t select_blocks(uint32_t n);
+uint64_t select_scratch_bytes(uint32_t n);
+int launch_select(const pcppx_batch* b, const pcppx_select_spec* spec, const pcppx_selection* out, void* scratch,
+                  hipStream_t stream);
 }  // namespace pcppx

@@ -154,6 +154,21 @@ class Engine:
                                                           abi.ptr(info), C.c_void_p(stream or 0)),
                   "pcppx_parse_batch_device_reasm")
 
+    def select_device(self, data, offsets, caplens, n: int, linktype: int, spec: abi.SelectSpec, out_offsets,
+                      out_caplens, totals, max_packets: int, out_data=None, data_cap: int = 0, out_index=None,
+                      stream: int | None = None, data_len: int | None = None) -> None:
+        """Queue pcppx_select_device over device tensors: the packets spec selects (abi.make_select_spec: a keep mask,
+        or the flags of a parse's summary / brief) are gathered in source order into out_data (u8, data_cap bytes; None
+        = index-only) with out_offsets (i64) / out_caplens (i32) / out_index (i32, optional) of max_packets entries;
+        totals: 8 x i64 (abi.SEL_*), overwritten. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        sel = abi.Selection(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+                            max_packets, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_select_device(self.ctx, C.byref(b), C.byref(spec), C.byref(sel),
+                                               C.c_void_p(stream or 0)), "pcppx_select_device")
+
     def filter_reset(self, capacity: int = 0) -> None:
         abi.check(self.lib.pcppx_filter_reset(self.ctx, capacity), "pcppx_filter_reset")
 
@@ -351,3 +366,51 @@ def parse_on_device(eng: Engine, batch: PacketBatch, opts: abi.Opts | None = Non
     eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, stream)
     torch.cuda.synchronize(device)
     return records_from_device(summary, layers, n, opts.max_layers)
+
+
+def select_on_device(eng: Engine, batch: PacketBatch, keep=None, flags=None, flags_any: int = 0, invert: bool = False,
+                     snaplen: int = 0, data_cap: int | None = None, max_packets: int | None = None,
+                     index_only: bool = False, device: str = "cuda:0"):
+    """Copy a host batch to HBM, gather the selected packets there (pcppx_select_device), copy the result back:
+    (PacketBatch of the written packets, index u32 = their source packet numbers, totals dict).
+    keep: n-byte mask (non-zero = selected), or flags: the batch's summary / brief record array (abi.SUMMARY_DTYPE /
+    abi.BRIEF_DTYPE) tested with flags_any. data_cap / max_packets default to the batch's bytes / packets.
+    index_only: no bytes move (the returned batch's data is empty, its offsets the would-be positions).
+    timestamps_ns and frame_lens follow the packets through index."""
+    import torch
+
+    if (keep is None) == (flags is None):
+        raise ValueError("give exactly one of keep and flags")
+    n = batch.n
+    data, offsets, caplens = to_device(batch, device)
+    if keep is not None:
+        sel_t = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(device)
+        spec = abi.make_select_spec(keep=abi.ptr(sel_t) if n else 1, invert=invert, snaplen=snaplen)
+    else:
+        rec = np.ascontiguousarray(flags)
+        if rec.dtype.itemsize not in (abi.BRIEF_DTYPE.itemsize, abi.SUMMARY_DTYPE.itemsize):
+            raise ValueError("flags must be a summary or a brief record array")
+        sel_t = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(device)
+        spec = abi.make_select_spec(flags=(abi.ptr(sel_t) if n else 0) + abi.FLAGS_OFFSET,
+                                    flags_stride=rec.dtype.itemsize, flags_any=flags_any, invert=invert, snaplen=snaplen)
+    cap = int(batch.caplens.sum(dtype=np.uint64)) if data_cap is None else data_cap
+    mp = n if max_packets is None else max_packets
+    out_data = None if index_only else torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    out_off = torch.empty(max(mp, 1), dtype=torch.int64, device=device)
+    out_cap = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_idx = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    totals = torch.empty(abi.SEL_TOTALS, dtype=torch.int64, device=device)
+    eng.select_device(data, offsets, caplens, n, batch.linktype, spec, out_off, out_cap, totals, mp, out_data, cap,
+                      out_idx, torch.cuda.current_stream(device).cuda_stream)
+    torch.cuda.synchronize(device)
+    tot = abi.totals_dict(totals.cpu().numpy().view(np.uint64))
+    w, wb = tot["written_packets"], tot["written_bytes"]
+    index = out_idx[:w].cpu().numpy().view(np.uint32)
+    out = PacketBatch(np.zeros(0, np.uint8) if index_only else out_data[:wb].cpu().numpy(),
+                      out_off[:w].cpu().numpy().view(np.uint64), out_cap[:w].cpu().numpy().view(np.uint32),
+                      batch.linktype)
+    if batch.timestamps_ns is not None:
+        out.timestamps_ns = batch.timestamps_ns[index]
+    if batch.frame_lens is not None:
+        out.frame_lens = batch.frame_lens[index]
+    return out, index, tot
