@@ -457,6 +457,81 @@ PCPPX_API int pcppx_select_device(pcppx_ctx* ctx, const pcppx_batch* batch, cons
 /* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
 PCPPX_API int pcppx_select_reference(const pcppx_batch* batch, const pcppx_select_spec* spec, pcppx_selection* out);
 
+/* ---- steer: stable K-way flow steering of a device batch into packed sub-batches (what RSS does on a NIC) ----
+ * FilterTraffic's worker rule (a packet matches if an earlier packet of its 5-tuple flow matched,
+ * AppWorkerThread.h:99-131) is well defined across cores only because RSS hands every flow to one RX queue.
+ * pcppx_steer_device is that step for packets in HBM: packet i goes to bucket[i] (column mode) or to
+ * key[i] % n_buckets (key mode: a parse's hash5 / hash2 column, or a reassembly ip_key), and the packets are moved
+ * bucket by bucket, each bucket in source order, into one packed batch: one radix pass of a counting sort whose
+ * payload is the packet bytes; select generalised from 2 ways to K. Added within ABI 7: new symbols only. */
+#define PCPPX_STEER_MAX_BUCKETS 256
+typedef struct pcppx_steer_spec {
+	const uint8_t* bucket; /* column mode: device, n bytes: packet i goes to bucket[i]; a value >= n_buckets means
+	                          "not steered" (dropped, counted; its descriptor is not read). NULL = key mode */
+	const void* key;       /* key mode: device address of packet 0's 32-bit key (&summary[0].hash5, &brief[0].hash5,
+	                          &tuples[0].hash5, flow_keys, &summary[0].hash2, &info[0].ip_key ...):
+	                          bucket = key % n_buckets */
+	uint32_t key_stride;   /* key mode: bytes between consecutive packets' keys: a multiple of 4, 4..256; the key
+	                          4-byte aligned (column mode: ignored) */
+	uint32_t n_buckets;    /* 1..PCPPX_STEER_MAX_BUCKETS */
+	uint32_t snaplen;      /* 0 = whole packet; else the output caplen is min(caplen, snaplen) */
+	uint32_t reserved;
+} pcppx_steer_spec;
+
+/* pcppx_steering.totals words */
+#define PCPPX_STEER_STEERED_PACKETS 0 /* packets with a bucket < n_buckets whose descriptor is in bounds */
+#define PCPPX_STEER_STEERED_BYTES 1   /* their output lengths (after snaplen) */
+#define PCPPX_STEER_DROPPED 2         /* column values >= n_buckets */
+#define PCPPX_STEER_BAD_DESC 3        /* packets with a bucket whose offsets[i] + caplens[i] > data_len (or wraps 64
+                                         bits): never read, never steered */
+#define PCPPX_STEER_OVERFLOW 4        /* 1: the steered packets / bytes exceed max_packets / data_cap; else 0 */
+#define PCPPX_STEER_TOTALS 8          /* words 5-7 zero */
+
+typedef struct pcppx_steering { /* all device pointers */
+	uint8_t* data;          /* packed bytes of the steered packets, back to back, no padding; NULL = index-only */
+	uint64_t data_cap;
+	uint64_t* offsets;      /* max_packets entries: offsets[r] = sum of the output lengths of output packets < r */
+	uint32_t* caplens;      /* max_packets entries */
+	uint32_t* index;        /* optional (NULL): index[r] = source packet number of output packet r */
+	uint32_t* bucket_first; /* n_buckets + 1 entries: bucket b = output packets [bucket_first[b], bucket_first[b+1]) */
+	uint64_t* bucket_pos;   /* n_buckets + 1 entries: its bytes = data[bucket_pos[b], bucket_pos[b+1]) */
+	uint32_t max_packets;
+	uint32_t reserved;
+	uint64_t* totals;       /* PCPPX_STEER_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_steering;
+
+/* Steered: packet i is steered iff its rule gives a bucket < n_buckets and offsets[i] + caplens[i] <= data_len (the
+ * 64-bit wrap checked too). A packet with a bucket that is out of bounds is never read and counts in BAD_DESC; a column
+ * value >= n_buckets counts in DROPPED (key mode drops nothing).
+ * Output order: bucket-major and stable. Bucket 0's steered packets in source order, then bucket 1's, and so on, back
+ * to back with no padding inside buckets or between them: offsets[r] is the sum of the output lengths of the output
+ * packets before r, bucket_first[n_buckets] = STEERED_PACKETS, bucket_pos[n_buckets] = STEERED_BYTES. The whole output
+ * is an ordinary pcppx_batch, and so is bucket b without a copy: the same data / data_len, offsets + bucket_first[b],
+ * caplens + bucket_first[b], n = bucket_first[b+1] - bucket_first[b].
+ * Capacity is all or nothing (unlike select's prefix rule: a prefix of a bucket-major output is useless): the output
+ * overflows iff STEERED_PACKETS > max_packets or, when data != NULL, STEERED_BYTES > data_cap. Then OVERFLOW = 1,
+ * totals / bucket_first / bucket_pos hold the full would-be values (size the buffers from them and call again) and
+ * data / offsets / caplens / index are not touched at all. max_packets = n and data_cap = the sum of the caplens
+ * always suffice. With data == NULL (index-only) no bytes move, the byte capacity is not applied and offsets hold the
+ * would-be positions.
+ * As select: a packet of any caplen (0, or above PCPPX_MAX_CAPLEN) is copied; the source batch may be gapped,
+ * unordered or overlapping; out->data must not overlap batch->data. Source bytes are read only through aligned 16-B
+ * granules (which never cross a page) that hold at least one byte of a steered packet. Nothing outside
+ * [0, STEERED_BYTES) of data and nothing outside the first STEERED_PACKETS entries of offsets / caplens / index is
+ * written. The output is a pure function of the inputs, bit-identical from run to run: every place comes from counts
+ * and scans, none from the order in which atomics land.
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, spec, out, totals, offsets, caplens, bucket_first or
+ * bucket_pos; bucket and key both null or both set; n_buckets 0 or above PCPPX_STEER_MAX_BUCKETS; key mode with a
+ * key_stride that is not a multiple of 4 in 4..256 or a key that is not 4-byte aligned; a non-zero reserved field.
+ * n == 0 is legal: zero totals, all-zero bucket_first / bucket_pos. The work is queued on hip_stream and the call
+ * returns without waiting (the totals stay on the device); calls on one context are ordered through its steer scratch
+ * (a buffer and an event of their own, as select's). Scratch: with g = ceil(n / 1024) blocks and K = n_buckets,
+ * 12 * K * g + 12 * K + 8 * g bytes (per bucket and block a 32-bit count and a 64-bit byte sum, the K bucket totals,
+ * two 32-bit counters per block); PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_steer_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_steer_spec* spec, pcppx_steering* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_steer_reference(const pcppx_batch* batch, const pcppx_steer_spec* spec, pcppx_steering* out);
+
 /* ---- host ingest: pcap / pcapng captures into packed batch buffers ---- */
 typedef struct pcppx_pcap pcppx_pcap;
 /* Open a capture; the format comes from its first 4 bytes as IFileReaderDevice::createReader

@@ -183,6 +183,42 @@ def select_reference(batch: Batch, spec: SelectSpec, out: Selection) -> None:
     check(load_engine().pcppx_select_reference(C.byref(batch), C.byref(spec), C.byref(out)), "pcppx_select_reference")
 
 
+# pcppx_steering.totals words (PCPPX_STEER_*)
+STEER_STEERED_PACKETS, STEER_STEERED_BYTES, STEER_DROPPED, STEER_BAD_DESC, STEER_OVERFLOW = 0, 1, 2, 3, 4
+STEER_TOTALS = 8
+STEER_MAX_BUCKETS = 256
+STEER_FIELDS = ("steered_packets", "steered_bytes", "dropped", "bad_desc", "overflow")
+
+
+class SteerSpec(C.Structure):
+    """pcppx_steer_spec: where pcppx_steer_device sends each packet (a bucket column, or a 32-bit key % n_buckets)."""
+    _fields_ = [("bucket", C.c_void_p), ("key", C.c_void_p), ("key_stride", C.c_uint32), ("n_buckets", C.c_uint32),
+                ("snaplen", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Steering(C.Structure):
+    """pcppx_steering: the bucket-major packed output batch, the source index, the bucket bounds and the totals."""
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("offsets", C.c_void_p), ("caplens", C.c_void_p),
+                ("index", C.c_void_p), ("bucket_first", C.c_void_p), ("bucket_pos", C.c_void_p),
+                ("max_packets", C.c_uint32), ("reserved", C.c_uint32), ("totals", C.c_void_p)]
+
+
+def make_steer_spec(bucket=None, key=None, key_stride: int = 4, n_buckets: int = 1, snaplen: int = 0) -> SteerSpec:
+    """bucket: address of the n-byte bucket column, or key: address of packet 0's 32-bit key (records + the field's
+    offset, e.g. SUMMARY_DTYPE.fields["hash5"][1]) with key_stride = the record size (4 for a plain u32 column)."""
+    return SteerSpec(bucket, key, key_stride if key is not None else 0, n_buckets, snaplen, 0)
+
+
+def steer_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(STEER_FIELDS)}
+
+
+def steer_reference(batch: Batch, spec: SteerSpec, out: Steering) -> None:
+    """pcppx_steer_reference: pcppx_steer_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_steer_reference(C.byref(batch), C.byref(spec), C.byref(out)), "pcppx_steer_reference")
+
+
 def ipv4_to_int(dotted: str) -> int:
     """IPv4Address::toInt(): the address bytes in memory order read as a little-endian u32."""
     b = bytes(int(x) for x in dotted.split("."))
@@ -326,6 +362,10 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_select_device.restype = C.c_int
     lib.pcppx_select_reference.argtypes = [C.POINTER(Batch), C.POINTER(SelectSpec), C.POINTER(Selection)]
     lib.pcppx_select_reference.restype = C.c_int
+    lib.pcppx_steer_device.argtypes = [P, C.POINTER(Batch), C.POINTER(SteerSpec), C.POINTER(Steering), P]
+    lib.pcppx_steer_device.restype = C.c_int
+    lib.pcppx_steer_reference.argtypes = [C.POINTER(Batch), C.POINTER(SteerSpec), C.POINTER(Steering)]
+    lib.pcppx_steer_reference.restype = C.c_int
     for name in ("pcppx_device_count", "pcppx_open", "pcppx_sync", "pcppx_parse_batch_device",
                  "pcppx_parse_batch_host", "pcppx_flow_count_device"):
         getattr(lib, name).restype = C.c_int
@@ -341,7 +381,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_flow_count_device", "pcppx_flow_count_keys_device", "pcppx_filter_device", "pcppx_filter_reset", "pcppx_filter_batch_host", "pcppx_reasm_device", "pcppx_parse_batch_device_reasm", "pcppx_pcap_open", "pcppx_pcap_linktype",
     "pcppx_pcap_read_batch", "pcppx_pcap_read_batch_ex", "pcppx_pcap_map_batch", "pcppx_pcap_close", "pcppx_host_alloc", "pcppx_host_free",
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
-    "pcppx_select_device", "pcppx_select_reference",
+    "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
 )
 
 

@@ -185,6 +185,11 @@ struct pcppx_ctx
 	uint64_t select_bytes = 0;
 	hipEvent_t select_done = nullptr;
 	bool select_pending = false;
+	// pcppx_steer_device: the block sums per bucket and the bucket totals (steer_scratch_bytes), ordered likewise
+	void* d_steer = nullptr;
+	uint64_t steer_bytes = 0;
+	hipEvent_t steer_done = nullptr;
+	bool steer_pending = false;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -879,6 +884,10 @@ extern "C"
 			(void)hipEventSynchronize(c->select_done);
 		if (c->d_select)
 			(void)hipFreeAsync(c->d_select, c->stream);
+		if (c->steer_pending)
+			(void)hipEventSynchronize(c->steer_done);
+		if (c->d_steer)
+			(void)hipFreeAsync(c->d_steer, c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -895,6 +904,8 @@ extern "C"
 			(void)hipEventDestroy(c->stats_done);
 		if (c->select_done)
 			(void)hipEventDestroy(c->select_done);
+		if (c->steer_done)
+			(void)hipEventDestroy(c->steer_done);
 		(void)hipStreamDestroy(c->stream);
 		delete c;
 	}
@@ -1288,6 +1299,136 @@ extern "C"
 		o->totals[PCPPX_SEL_WRITTEN_PACKETS] = written;
 		o->totals[PCPPX_SEL_WRITTEN_BYTES] = written_bytes;
 		o->totals[PCPPX_SEL_BAD_DESC] = bad;
+		return PCPPX_OK;
+	}
+}
+
+namespace
+{
+// the argument rules pcppx_steer_device and pcppx_steer_reference share (include/pcppx.h)
+bool valid_steer(const pcppx_batch* b, const pcppx_steer_spec* s, const pcppx_steering* o)
+{
+	if (b == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
+	    o->caplens == nullptr || o->bucket_first == nullptr || o->bucket_pos == nullptr)
+		return false;
+	if ((s->bucket == nullptr) == (s->key == nullptr))
+		return false;
+	if (s->n_buckets == 0 || s->n_buckets > PCPPX_STEER_MAX_BUCKETS)
+		return false;
+	if (s->key != nullptr && (s->key_stride < 4 || s->key_stride > 256 || s->key_stride % 4 != 0 ||
+	                          reinterpret_cast<uintptr_t>(s->key) % 4 != 0))
+		return false;
+	if (s->reserved != 0 || o->reserved != 0)
+		return false;
+	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_steer_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_steer_spec* s, pcppx_steering* o,
+	                       void* hip_stream)
+	{
+		if (c == nullptr || !valid_steer(b, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_STEER_TOTALS * sizeof(uint64_t), st)) &&
+			               ok(hipMemsetAsync(o->bucket_first, 0, (s->n_buckets + 1) * sizeof(uint32_t), st)) &&
+			               ok(hipMemsetAsync(o->bucket_pos, 0, (s->n_buckets + 1) * sizeof(uint64_t), st))
+			           ? PCPPX_OK
+			           : PCPPX_E_HIP;
+		// the context's previous steer (possibly queued on another stream) owns the block sums until steer_done
+		int rc = ensure_scratch(st, &c->d_steer, &c->steer_bytes, pcppx::steer_scratch_bytes(b->n, s->n_buckets),
+		                        &c->steer_done, c->steer_pending);
+		if (rc != PCPPX_OK)
+			return rc;
+		rc = pcppx::launch_steer(b, s, o, c->d_steer, st);
+		if (rc != PCPPX_OK)
+			return rc;
+		if (!ok(hipEventRecord(c->steer_done, st)))
+			return PCPPX_E_HIP;
+		c->steer_pending = true;
+		return PCPPX_OK;
+	}
+
+	int pcppx_steer_reference(const pcppx_batch* b, const pcppx_steer_spec* s, pcppx_steering* o)
+	{
+		if (!valid_steer(b, s, o))
+			return PCPPX_E_INVAL;
+		const uint32_t K = s->n_buckets;
+		constexpr uint32_t kNone = 0xFFFFFFFFu;
+		uint64_t dropped = 0, bad = 0;
+		// pass 1: every packet's bucket (kNone: not steered) and output length; the buckets' packets and bytes
+		std::vector<uint32_t> bucket(b->n), len(b->n), first(K + 1, 0);
+		std::vector<uint64_t> pos(K + 1, 0);
+		for (uint32_t i = 0; i < b->n; ++i)
+		{
+			uint32_t v;
+			if (s->bucket != nullptr)
+				v = s->bucket[i];
+			else
+			{
+				std::memcpy(&v, static_cast<const uint8_t*>(s->key) + (size_t)i * s->key_stride, sizeof(v));
+				v %= K;
+			}
+			bucket[i] = kNone;
+			len[i] = 0;
+			if (v >= K)
+			{
+				++dropped;
+				continue;
+			}
+			const uint64_t off = b->offsets[i];
+			const uint32_t cap = b->caplens[i];
+			if (off + cap < off || off + cap > b->data_len)
+			{
+				++bad;
+				continue;
+			}
+			bucket[i] = v;
+			len[i] = (s->snaplen != 0 && cap > s->snaplen) ? s->snaplen : cap;
+			++first[v + 1];
+			pos[v + 1] += len[i];
+		}
+		for (uint32_t k = 0; k < K; ++k)
+		{
+			first[k + 1] += first[k];
+			pos[k + 1] += pos[k];
+		}
+		const bool overflow = first[K] > o->max_packets || (o->data != nullptr && pos[K] > o->data_cap);
+		for (uint32_t k = 0; k <= K; ++k)
+		{
+			o->bucket_first[k] = first[k];
+			o->bucket_pos[k] = pos[k];
+		}
+		for (int k = 0; k < PCPPX_STEER_TOTALS; ++k)
+			o->totals[k] = 0;
+		o->totals[PCPPX_STEER_STEERED_PACKETS] = first[K];
+		o->totals[PCPPX_STEER_STEERED_BYTES] = pos[K];
+		o->totals[PCPPX_STEER_DROPPED] = dropped;
+		o->totals[PCPPX_STEER_BAD_DESC] = bad;
+		o->totals[PCPPX_STEER_OVERFLOW] = overflow ? 1 : 0;
+		if (overflow)  // all or nothing
+			return PCPPX_OK;
+		// pass 2: each packet behind the packets of its bucket before it (first / pos: the buckets' next places)
+		for (uint32_t i = 0; i < b->n; ++i)
+		{
+			const uint32_t v = bucket[i];
+			if (v == kNone)
+				continue;
+			const uint32_t r = first[v]++;
+			const uint64_t p = pos[v];
+			pos[v] += len[i];
+			o->offsets[r] = p;
+			o->caplens[r] = len[i];
+			if (o->index != nullptr)
+				o->index[r] = i;
+			if (o->data != nullptr && len[i] != 0)
+				std::memcpy(o->data + p, b->data + b->offsets[i], len[i]);
+		}
 		return PCPPX_OK;
 	}
 }

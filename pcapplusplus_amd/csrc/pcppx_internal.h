@@ -45,4 +45,14 @@ uint32_t select_blocks(uint32_t n);
 uint64_t select_scratch_bytes(uint32_t n);
 int launch_select(const pcppx_batch* b, const pcppx_select_spec* spec, const pcppx_selection* out, void* scratch,
                   hipStream_t stream);
+// pcppx_steer_device (pcppx_steer.hip): count, per-bucket scan, bucket bases and copy, four launches on `stream`.
+// scratch: steer_scratch_bytes(n, n_buckets) bytes (the block sums per bucket, bucket-major, and the bucket totals);
+// one block steers kSteerBlockPk packets, a scan step takes kSteerScanStep block sums. Arguments are checked by the
+// caller; n > 0.
+constexpr uint32_t kSteerBlockPk = 1024;
+constexpr uint32_t kSteerScanStep = 64;
+uint32_t steer_blocks(uint32_t n);
+uint64_t steer_scratch_bytes(uint32_t n, uint32_t n_buckets);
+int launch_steer(const pcppx_batch* b, const pcppx_steer_spec* spec, const pcppx_steering* out, void* scratch,
+                 hipStream_t stream);
 }  // namespace pcppx

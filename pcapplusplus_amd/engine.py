@@ -169,6 +169,23 @@ class Engine:
         abi.check(self.lib.pcppx_select_device(self.ctx, C.byref(b), C.byref(spec), C.byref(sel),
                                                C.c_void_p(stream or 0)), "pcppx_select_device")
 
+    def steer_device(self, data, offsets, caplens, n: int, linktype: int, spec: abi.SteerSpec, out_offsets,
+                     out_caplens, bucket_first, bucket_pos, totals, max_packets: int, out_data=None, data_cap: int = 0,
+                     out_index=None, stream: int | None = None, data_len: int | None = None) -> None:
+        """Queue pcppx_steer_device over device tensors: the packets go, bucket by bucket (abi.make_steer_spec: a
+        bucket column, or a 32-bit key % n_buckets) and in source order inside a bucket, into out_data (u8, data_cap
+        bytes; None = index-only) with out_offsets (i64) / out_caplens (i32) / out_index (i32, optional) of max_packets
+        entries; bucket_first (i32) / bucket_pos (i64): n_buckets + 1 entries; totals: 8 x i64 (abi.STEER_*),
+        overwritten. All or nothing: on overflow only totals / bucket_first / bucket_pos are written. Returns without
+        waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        out = abi.Steering(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+                           abi.ptr(bucket_first), abi.ptr(bucket_pos), max_packets, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_steer_device(self.ctx, C.byref(b), C.byref(spec), C.byref(out),
+                                              C.c_void_p(stream or 0)), "pcppx_steer_device")
+
     def filter_reset(self, capacity: int = 0) -> None:
         abi.check(self.lib.pcppx_filter_reset(self.ctx, capacity), "pcppx_filter_reset")
 
@@ -414,3 +431,72 @@ def select_on_device(eng: Engine, batch: PacketBatch, keep=None, flags=None, fla
     if batch.frame_lens is not None:
         out.frame_lens = batch.frame_lens[index]
     return out, index, tot
+
+
+def steer_on_device(eng: Engine, batch: PacketBatch, bucket=None, key=None, key_field: str = "hash5",
+                    n_buckets: int = 1, snaplen: int = 0, data_cap: int | None = None, max_packets: int | None = None,
+                    index_only: bool = False, device: str = "cuda:0"):
+    """Copy a host batch to HBM, steer its packets there into n_buckets packed sub-batches (pcppx_steer_device), copy
+    the result back: (PacketBatch of the steered packets, bucket-major and stable; index u32 = their source packet
+    numbers; bucket_first u32[n_buckets + 1]; bucket_pos u64[n_buckets + 1]; totals dict).
+    bucket: n-byte column (a value >= n_buckets drops the packet), or key: a summary / brief / tuple record array
+    (abi.SUMMARY_DTYPE / BRIEF_DTYPE / TUPLE_DTYPE or any structured array with key_field, a 32-bit field: "hash5",
+    "hash2", "ip_key" ...) or a plain u32 column; the bucket is key % n_buckets. data_cap / max_packets default to the
+    batch's bytes / packets (always enough). All or nothing: when totals["overflow"] is set the returned batch and
+    index are empty and bucket_first / bucket_pos hold the sizes to call again with. index_only: no bytes move (the
+    returned batch's data is empty, its offsets the would-be positions). timestamps_ns and frame_lens follow the
+    packets through index (bucket_batch() keeps them per bucket)."""
+    import torch
+
+    if (bucket is None) == (key is None):
+        raise ValueError("give exactly one of bucket and key")
+    n = batch.n
+    data, offsets, caplens = to_device(batch, device)
+    if bucket is not None:
+        rule_t = torch.from_numpy(np.ascontiguousarray(bucket, dtype=np.uint8)).to(device)
+        spec = abi.make_steer_spec(bucket=abi.ptr(rule_t) if n else 4, n_buckets=n_buckets, snaplen=snaplen)
+    else:
+        rec = np.ascontiguousarray(key)
+        if rec.dtype.names is None:
+            if rec.dtype.itemsize != 4:
+                raise ValueError("a plain key column must be 32-bit")
+            field_off = 0
+        else:
+            ft, field_off = rec.dtype.fields[key_field][:2]
+            if ft.itemsize != 4:
+                raise ValueError(f"{key_field} is not a 32-bit field")
+        rule_t = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(device)
+        spec = abi.make_steer_spec(key=(abi.ptr(rule_t) if n else 4) + field_off, key_stride=rec.dtype.itemsize,
+                                   n_buckets=n_buckets, snaplen=snaplen)
+    cap = int(batch.caplens.sum(dtype=np.uint64)) if data_cap is None else data_cap
+    mp = n if max_packets is None else max_packets
+    out_data = None if index_only else torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    out_off = torch.empty(max(mp, 1), dtype=torch.int64, device=device)
+    out_cap = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_idx = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    first = torch.empty(n_buckets + 1, dtype=torch.int32, device=device)
+    pos = torch.empty(n_buckets + 1, dtype=torch.int64, device=device)
+    totals = torch.empty(abi.STEER_TOTALS, dtype=torch.int64, device=device)
+    eng.steer_device(data, offsets, caplens, n, batch.linktype, spec, out_off, out_cap, first, pos, totals, mp,
+                     out_data, cap, out_idx, torch.cuda.current_stream(device).cuda_stream)
+    torch.cuda.synchronize(device)
+    tot = abi.steer_totals_dict(totals.cpu().numpy().view(np.uint64))
+    w, wb = (0, 0) if tot["overflow"] else (tot["steered_packets"], tot["steered_bytes"])
+    index = out_idx[:w].cpu().numpy().view(np.uint32)
+    out = PacketBatch(np.zeros(0, np.uint8) if index_only else out_data[:wb].cpu().numpy(),
+                      out_off[:w].cpu().numpy().view(np.uint64), out_cap[:w].cpu().numpy().view(np.uint32),
+                      batch.linktype)
+    if batch.timestamps_ns is not None:
+        out.timestamps_ns = batch.timestamps_ns[index]
+    if batch.frame_lens is not None:
+        out.frame_lens = batch.frame_lens[index]
+    return out, index, first.cpu().numpy().view(np.uint32), pos.cpu().numpy().view(np.uint64), tot
+
+
+def bucket_batch(out: PacketBatch, bucket_first, b: int) -> PacketBatch:
+    """Bucket b of a steered batch as a PacketBatch view (no copy): the same data, the bucket's rows of offsets /
+    caplens (and of timestamps_ns / frame_lens, which followed the packets through index)."""
+    lo, hi = int(bucket_first[b]), int(bucket_first[b + 1])
+    cut = lambda a: None if a is None else a[lo:hi]  # noqa: E731
+    return PacketBatch(out.data, out.offsets[lo:hi], out.caplens[lo:hi], out.linktype, cut(out.timestamps_ns),
+                       cut(out.frame_lens))

@@ -1,0 +1,411 @@
+"""Case generators and runners for pcppx_steer_device / pcppx_steer_reference (tests/test_steer.py).
+
+A Case is a source batch (bytes + descriptors, possibly gapped, shuffled, overlapping or out of bounds), a steering
+rule (a bucket column, or key records + stride + offset; n_buckets; snaplen) and the output's capacities. Three runners
+produce the same Buffers from it -- brute() (a per-packet Python loop: the contract of include/pcppx.h restated),
+run_reference() (pcppx_steer_reference) and run_device() (pcppx_steer_device) -- every buffer pre-filled with 0xA5 and
+over-allocated by 64 B / 4 entries, so equality of the whole buffers also shows that nothing beyond STEERED_* was
+touched, and nothing at all on overflow.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field, replace
+
+import numpy as np
+
+from pcapplusplus_amd import abi
+from select_cases import FILL, PAD_BYTES, PAD_ENTRIES, mix_lens, packed
+
+BLOCK = 1024    # packets per block of the count and copy kernels (pcppx_internal.h kSteerBlockPk)
+SCAN_STEP = 64  # block sums per step of the per-bucket scan (pcppx_internal.h kSteerScanStep)
+BUCKET_STEP = 64  # buckets per step of the one-wave bucket-base scan (one per lane)
+F32, F64 = 0xA5A5A5A5, 0xA5A5A5A5A5A5A5A5
+
+
+@dataclass
+class Case:
+    name: str
+    data: np.ndarray      # u8
+    offsets: np.ndarray   # u64
+    caplens: np.ndarray   # u32
+    n_buckets: int = 1
+    bucket: np.ndarray | None = None  # u8[n]; None = key mode
+    key: np.ndarray | None = None     # key mode: the records' bytes (u8, n * key_stride), the key at key_offset
+    key_stride: int = 4
+    key_offset: int = 0
+    snaplen: int = 0
+    data_len: int | None = None       # None: len(data)
+    data_cap: int | None = None       # None: the bytes of the whole batch (always enough)
+    max_packets: int | None = None    # None: n
+    index_only: bool = False
+    want_index: bool = True
+    out_misalign: int = 0             # device runs: out->data starts this many bytes past a 16-B boundary
+    src_misalign: int = 0             # device runs: batch->data likewise
+    meta: dict = field(default_factory=dict)
+
+    @property
+    def n(self) -> int:
+        return len(self.caplens)
+
+    def dlen(self) -> int:
+        return len(self.data) if self.data_len is None else self.data_len
+
+    def cap(self) -> int:
+        if self.data_cap is not None:
+            return self.data_cap
+        dl = np.uint64(self.dlen())
+        room = dl - np.minimum(self.offsets, dl)  # no 64-bit wrap: the bytes from the offset to data_len
+        ok = (self.offsets <= dl) & (self.caplens.astype(np.uint64) <= room)  # the in-bounds packets
+        return int(self.caplens[ok].astype(np.uint64).sum())
+
+    def maxp(self) -> int:
+        return self.n if self.max_packets is None else self.max_packets
+
+    def keys(self) -> np.ndarray:
+        """Key mode: the n 32-bit keys."""
+        rec = self.key[: self.n * self.key_stride].reshape(self.n, self.key_stride)
+        return np.ascontiguousarray(rec[:, self.key_offset:self.key_offset + 4]).view("<u4").reshape(-1)
+
+    def buckets(self) -> np.ndarray:
+        """The rule alone (before the bounds check): every packet's bucket value as an integer (>= n_buckets: dropped)."""
+        if self.bucket is not None:
+            return self.bucket.astype(np.int64)
+        return (self.keys() % np.uint32(self.n_buckets)).astype(np.int64)
+
+
+@dataclass
+class Buffers:
+    data: np.ndarray | None
+    offsets: np.ndarray
+    caplens: np.ndarray
+    index: np.ndarray | None
+    bucket_first: np.ndarray
+    bucket_pos: np.ndarray
+    totals: np.ndarray
+
+
+FIELDS = ("offsets", "caplens", "index", "bucket_first", "bucket_pos", "data")
+
+
+def alloc(c: Case) -> Buffers:
+    return Buffers(None if c.index_only else np.full(c.cap() + PAD_BYTES, FILL, np.uint8),
+                   np.full(c.maxp() + PAD_ENTRIES, F64, np.uint64),
+                   np.full(c.maxp() + PAD_ENTRIES, F32, np.uint32),
+                   np.full(c.maxp() + PAD_ENTRIES, F32, np.uint32) if c.want_index else None,
+                   np.full(c.n_buckets + 1 + PAD_ENTRIES, F32, np.uint32),
+                   np.full(c.n_buckets + 1 + PAD_ENTRIES, F64, np.uint64),
+                   np.full(abi.STEER_TOTALS, F64, np.uint64))
+
+
+def brute(c: Case) -> Buffers:
+    """include/pcppx.h's steer contract, one packet at a time."""
+    out = alloc(c)
+    K, data_len = c.n_buckets, c.dlen()
+    per = [[] for _ in range(K)]  # per bucket: (source packet, source offset, output length), in source order
+    dropped = bad = 0
+    for i, v in enumerate(c.buckets().tolist()):
+        if v >= K:
+            dropped += 1  # its descriptor is not looked at
+            continue
+        off, cap = int(c.offsets[i]), int(c.caplens[i])
+        if off + cap > data_len:  # Python integers: no wrap (the C code checks the 64-bit wrap too)
+            bad += 1
+            continue
+        per[v].append((i, off, min(cap, c.snaplen) if c.snaplen else cap))
+    r = p = 0
+    for b in range(K):
+        out.bucket_first[b], out.bucket_pos[b] = r, p
+        r += len(per[b])
+        p += sum(x[2] for x in per[b])
+    out.bucket_first[K], out.bucket_pos[K] = r, p
+    overflow = r > c.maxp() or (not c.index_only and p > c.cap())
+    out.totals[:] = 0
+    out.totals[:5] = (r, p, dropped, bad, int(overflow))
+    if overflow:
+        return out
+    r = p = 0
+    for b in range(K):
+        for i, off, ln in per[b]:
+            out.offsets[r] = p
+            out.caplens[r] = ln
+            if out.index is not None:
+                out.index[r] = i
+            if not c.index_only:
+                out.data[p:p + ln] = c.data[off:off + ln]
+            r += 1
+            p += ln
+    return out
+
+
+def _rule(c: Case) -> np.ndarray:
+    rule = np.ascontiguousarray(c.bucket if c.bucket is not None else c.key)
+    return rule if len(rule) else np.zeros(64, np.uint8)  # a non-null address for an empty batch
+
+
+def _spec(c: Case, addr: int) -> abi.SteerSpec:
+    if c.bucket is not None:
+        return abi.make_steer_spec(bucket=addr, n_buckets=c.n_buckets, snaplen=c.snaplen)
+    return abi.make_steer_spec(key=addr + c.key_offset, key_stride=c.key_stride, n_buckets=c.n_buckets,
+                               snaplen=c.snaplen)
+
+
+def run_reference(c: Case) -> Buffers:
+    out = alloc(c)
+    rule = _rule(c)
+    data = c.data if len(c.data) else np.zeros(1, np.uint8)
+    b = abi.Batch(data.ctypes.data, c.offsets.ctypes.data, c.caplens.ctypes.data, c.dlen(), c.n, 1, 0)
+    st = abi.Steering(None if c.index_only else out.data.ctypes.data, c.cap(), out.offsets.ctypes.data,
+                      out.caplens.ctypes.data, out.index.ctypes.data if out.index is not None else None,
+                      out.bucket_first.ctypes.data, out.bucket_pos.ctypes.data, c.maxp(), 0, out.totals.ctypes.data)
+    abi.steer_reference(b, _spec(c, rule.ctypes.data), st)
+    return out
+
+
+class DeviceRun:
+    """A case's tensors on the device; launch() queues pcppx_steer_device on a stream, result() reads the buffers."""
+
+    def __init__(self, c: Case, device: str = "cuda:0"):
+        import torch
+
+        self.c, self.device = c, device
+        host = alloc(c)
+        up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+        src = c.data if len(c.data) else np.zeros(1, np.uint8)
+        self.s_raw = up(np.concatenate([np.zeros(16 + c.src_misalign, np.uint8), src]))
+        self.data = self.s_raw[16 + c.src_misalign:]
+        assert self.data.data_ptr() % 16 == c.src_misalign
+        self.offsets, self.caplens = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32))
+        self.rule = up(_rule(c))
+        mis = c.out_misalign
+        self.d_raw = None if c.index_only else up(np.concatenate([np.full(16 + mis, FILL, np.uint8), host.data]))
+        self.d_data = None if c.index_only else self.d_raw[16 + mis:]
+        if self.d_data is not None:
+            assert self.d_data.data_ptr() % 16 == mis
+        self.d_off, self.d_cap = up(host.offsets.view(np.int64)), up(host.caplens.view(np.int32))
+        self.d_idx = up(host.index.view(np.int32)) if host.index is not None else None
+        self.d_first, self.d_pos = up(host.bucket_first.view(np.int32)), up(host.bucket_pos.view(np.int64))
+        self.d_tot = up(host.totals.view(np.int64))
+
+    def launch(self, engine, stream: int) -> None:
+        c = self.c
+        engine.steer_device(self.data, self.offsets, self.caplens, c.n, 1, _spec(c, abi.ptr(self.rule)), self.d_off,
+                            self.d_cap, self.d_first, self.d_pos, self.d_tot, c.maxp(), self.d_data, c.cap(), self.d_idx,
+                            stream, data_len=c.dlen())
+
+    def result(self) -> Buffers:
+        import torch
+
+        torch.cuda.synchronize(self.device)
+        mis = self.c.out_misalign
+        if self.d_raw is not None:  # the bytes in front of out->data belong to someone else
+            assert bool((self.d_raw[:16 + mis] == FILL).all()), "bytes before out->data were written"
+        dn = lambda t, dt: t.cpu().numpy().view(dt)  # noqa: E731
+        return Buffers(None if self.d_data is None else dn(self.d_data, np.uint8), dn(self.d_off, np.uint64),
+                       dn(self.d_cap, np.uint32), None if self.d_idx is None else dn(self.d_idx, np.uint32),
+                       dn(self.d_first, np.uint32), dn(self.d_pos, np.uint64), dn(self.d_tot, np.uint64))
+
+
+def run_device(engine, c: Case, device: str = "cuda:0") -> Buffers:
+    import torch
+
+    run = DeviceRun(c, device)
+    run.launch(engine, torch.cuda.current_stream(device).cuda_stream)
+    return run.result()
+
+
+def assert_same(got: Buffers, want: Buffers, what: str) -> None:
+    """Whole buffers, pads included: the written part equal, the 0xA5 fill intact everywhere else."""
+    assert list(got.totals) == list(want.totals), (what, "totals", list(got.totals), list(want.totals))
+    for f in FIELDS:
+        g, w = getattr(got, f), getattr(want, f)
+        assert (g is None) == (w is None), (what, f)
+        if g is None:
+            continue
+        assert g.shape == w.shape, (what, f, g.shape, w.shape)
+        bad = np.nonzero(g != w)[0]
+        assert len(bad) == 0, (what, f, len(bad), "first at", int(bad[0]), int(g[bad[0]]), int(w[bad[0]]))
+
+
+def assert_untouched(got: Buffers, what: str) -> None:
+    """The all-or-nothing rule: data, offsets, caplens and index still hold the fill, every byte of them."""
+    for f, fill in (("data", FILL), ("offsets", F64), ("caplens", F32), ("index", F32)):
+        g = getattr(got, f)
+        assert g is None or bool((g == fill).all()), (what, f)
+
+
+# ------------------------------------------------------------------ generators
+def column(n: int, K: int, pattern: str, seed: int = 0) -> np.ndarray:
+    rng = np.random.default_rng(seed)
+    i = np.arange(n)
+    if pattern == "random":
+        b = rng.integers(0, K, n)
+    elif pattern == "one":        # all packets in one (a middle) bucket
+        b = np.full(n, K // 2)
+    elif pattern == "first_empty":
+        b = rng.integers(1, K, n) if K > 1 else np.zeros(n)
+    elif pattern == "last_empty":
+        b = rng.integers(0, max(K - 1, 1), n)
+    elif pattern == "middle_empty":
+        b = rng.integers(0, max(K - 1, 1), n)
+        b[b >= K // 2] += 1
+    elif pattern == "round_robin":  # every lane of a wave another bucket (K >= 64)
+        b = i % K
+    elif pattern == "sorted":
+        b = np.sort(rng.integers(0, K, n))
+    elif pattern == "reverse":
+        b = np.sort(rng.integers(0, K, n))[::-1]
+    elif pattern == "single_last":  # one packet in the last bucket, the rest in bucket 0
+        b = np.zeros(n)
+        b[n // 2] = K - 1
+    elif pattern == "some_dropped":  # values >= K, 255 among them
+        b = rng.integers(0, K, n)
+        b[rng.random(n) < 0.2] = K
+        b[rng.random(n) < 0.1] = 255
+        b[rng.random(n) < 0.05] = min(K + 100, 255)
+    elif pattern == "all_dropped":
+        b = np.where(i % 2 == 0, K, 255)
+    else:
+        raise ValueError(pattern)
+    return np.asarray(b).astype(np.uint8)
+
+
+def make(name: str, lens, K: int = 8, pattern: str = "random", seed: int = 1, **kw) -> Case:
+    layout = {k: kw.pop(k) for k in ("start", "gaps", "tail") if k in kw}
+    data, offs, lens = packed(lens, seed, **layout)
+    return Case(name, data, offs, lens, n_buckets=K, bucket=column(len(lens), K, pattern, seed + 100), **kw)
+
+
+def with_keys(c: Case, keys: np.ndarray, stride: int, offset: int, seed: int = 5) -> Case:
+    """The same batch in key mode: random records of `stride` bytes with the 32-bit key at `offset`."""
+    rec = np.random.default_rng(seed).integers(0, 256, (c.n, stride), dtype=np.uint8)
+    rec[:, offset:offset + 4] = np.ascontiguousarray(keys.astype("<u4")).view(np.uint8).reshape(c.n, 4)
+    return replace(c, bucket=None, key=rec.reshape(-1), key_stride=stride, key_offset=offset)
+
+
+def steered_totals(c: Case):
+    t = brute(replace(c, data_cap=None, max_packets=None, index_only=True)).totals
+    return int(t[abi.STEER_STEERED_PACKETS]), int(t[abi.STEER_STEERED_BYTES])
+
+
+def small_lens(n: int, seed: int) -> np.ndarray:
+    """1-8 B packets: the large-n cases stay small in bytes."""
+    return np.random.default_rng(seed).integers(1, 9, n).astype(np.uint32)
+
+
+def aligned_grid() -> tuple[list[int], list[int]]:
+    """Lengths 0-47, each at all 16 source alignments: (lens, gaps) for packed()."""
+    lens, gaps, pos = [], [], 0
+    for ln in range(48):
+        for a in range(16):
+            gap = (a - pos) % 16
+            lens.append(ln)
+            gaps.append(gap)
+            pos += gap + ln
+    return lens, gaps
+
+
+BIG_N = (SCAN_STEP + 6) * BLOCK + 5  # 70 blocks and a partial one: every scan loop runs a second step
+
+
+def cases() -> list[Case]:
+    out: list[Case] = []
+    # n: the tile and block edges
+    for n in (0, 1, 63, 64, 65, BLOCK - 1, BLOCK, BLOCK + 1, 3 * BLOCK + 5):
+        out.append(make(f"n{n}", mix_lens(n, 40, n), 8, "random", seed=n))
+        out.append(make(f"n{n}_k3_drops", mix_lens(n, 40, n + 1), 3, "some_dropped", seed=n + 1))
+    # more blocks than one step of the per-bucket scan and of the dropped / bad sums, more buckets than one step of the
+    # bucket-base scan: each of those loops carries into a second step
+    out.append(make("big_k256", small_lens(BIG_N, 9), 256, "random", seed=9))
+    out.append(make("big_k255_drops", small_lens(BIG_N, 10), 255, "some_dropped", seed=10))
+    out.append(make("big_k8_rr", small_lens(BIG_N, 11), 8, "round_robin", seed=11))
+    c = make("big_k7_keys_bad", small_lens(BIG_N, 12), 7, "random", seed=12)
+    offs = c.offsets.copy()
+    offs[3::997] = np.uint64(len(c.data))  # bad descriptors in many blocks (every length is >= 1)
+    out.append(with_keys(replace(c, offsets=offs), np.random.default_rng(13).integers(0, 1 << 32, c.n), 16, 4))
+    # K
+    for K in (1, 2, 3, 7, 8, 64, 255, 256):
+        out.append(make(f"k{K}", mix_lens(1500, 100, K), K, "random", seed=K))
+    # bucket patterns
+    for K, pat in ((8, "one"), (8, "first_empty"), (8, "last_empty"), (8, "middle_empty"), (3, "middle_empty"),
+                   (64, "round_robin"), (256, "round_robin"), (7, "round_robin"), (8, "sorted"), (8, "reverse"),
+                   (256, "sorted"), (64, "reverse"), (8, "single_last"), (256, "single_last"), (8, "some_dropped"),
+                   (2, "some_dropped"), (255, "some_dropped"), (8, "all_dropped"), (1, "all_dropped")):
+        out.append(make(f"pat_{pat}_k{K}", mix_lens(1300, 120, K + 30), K, pat, seed=K + 30))
+    # key mode: K not a power of two, so that % is a modulo; the edge keys; every stride, the key inside the record
+    for K in (7, 255, 3):
+        base = make(f"keys_k{K}", mix_lens(900, 90, K + 60), K, "random", seed=K + 60)
+        keys = np.random.default_rng(K).integers(0, 1 << 32, base.n, dtype=np.uint64)
+        keys[:10] = [0, 1, K - 1, K, 0xFFFFFFFF, K + 1, 2 * K, 2 * K - 1, 0xFFFFFFFE, 0x80000000]
+        keys[-5:] = [0xFFFFFFFF, K, K - 1, 1, 0]
+        for stride, off in ((4, 0), (16, 4), (32, 8), (48, 40), (256, 252)):
+            out.append(replace(with_keys(base, keys, stride, off), name=f"keys_k{K}_stride{stride}"))
+    out.append(replace(with_keys(make("keys_k8_snap", mix_lens(500, 200, 77), 8, seed=77),
+                                 np.arange(500) * 2654435761 % (1 << 32), 32, 0), snaplen=60))
+    # lengths 0-47 at all 16 source alignments, crossed with destination misalignments (and a misaligned source base)
+    lens, gaps = aligned_grid()
+    for mis in (0, 1, 7, 15):
+        out.append(make(f"grid_dst{mis}", lens, 3, "random", seed=80 + mis, gaps=gaps, out_misalign=mis))
+        out.append(make(f"grid_dst{mis}_k1", lens, 1, "random", seed=90 + mis, gaps=gaps, out_misalign=mis))
+    out.append(make("grid_src5_dst9", lens, 5, "random", seed=99, gaps=gaps, out_misalign=9, src_misalign=5))
+    for s in (1, 8, 15):
+        out.append(make(f"start{s}", mix_lens(300, 100, 20 + s), 4, "random", seed=20 + s, start=s))
+    # runs of zero-length packets
+    z = mix_lens(1200, 60, 33)
+    z[100:300] = 0
+    z[640:705] = 0
+    z[-70:] = 0
+    out.append(make("zero_runs", z, 5, "random", seed=33))
+    out.append(make("all_zero_len", np.zeros(700, np.uint32), 6, "random", seed=34))
+    # long packets
+    out.append(make("len_jumbo", [64, 9000, 64, 65535, 64, 70000, 64, 9000, 3], 2, "random", seed=7))
+    out.append(make("len_jumbo_k1", [9000, 65535, 70000], 1, "random", seed=8))
+    out.append(make("len_jumbo_rev", [64, 9000, 64, 65535, 64, 70000, 64, 9000, 3], 3, "reverse", seed=7,
+                    out_misalign=3))
+    out.append(make("len_mix2000", mix_lens(900, 2000, 8), 8, "random", seed=8))
+    for ln in (64, 512, 1500):
+        out.append(make(f"len_{ln}", np.full(200, ln), 8, "random", seed=ln))
+    # source layout: gaps, unordered and overlapping descriptors; `tail` 0 everywhere, so the last packet ends exactly at
+    # data_len
+    out.append(make("gapped", mix_lens(600, 200, 40), 8, "random", seed=40, gaps=mix_lens(600, 40, 41)))
+    c = make("shuffled", mix_lens(600, 200, 42), 8, "random", seed=42)
+    perm = np.random.default_rng(43).permutation(c.n)
+    out.append(replace(c, offsets=c.offsets[perm], caplens=c.caplens[perm]))
+    c = make("overlap", mix_lens(300, 200, 44), 8, "random", seed=44)
+    twice = np.repeat(np.arange(c.n), 2)  # two descriptors over the same bytes ...
+    offs, lens2 = c.offsets[twice].copy(), c.caplens[twice].copy()
+    offs[1::2] += np.minimum(lens2[1::2], 3)  # ... the second one starting inside the first
+    lens2[1::2] -= np.minimum(lens2[1::2], 3)
+    out.append(replace(c, offsets=offs, caplens=lens2, bucket=column(len(lens2), 8, "random", 45)))
+    # bad descriptors, inside steered buckets and inside dropped ones: past the end, a huge caplen, an end that wraps
+    for K, pat in ((8, "random"), (5, "some_dropped"), (8, "all_dropped")):
+        c = make(f"bad_desc_{pat}_k{K}", mix_lens(900, 120, 70), K, pat, seed=70)
+        offs, lens2 = c.offsets.copy(), c.caplens.copy()
+        offs[5::37] = len(c.data) - 1
+        lens2[5::37] = np.maximum(lens2[5::37], 2)
+        lens2[11::53] = 0xFFFFFFF0
+        offs[17::101] = np.uint64(0xFFFFFFFFFFFFFFF0)
+        lens2[17::101] = 64
+        offs[64] = len(c.data)  # an empty packet at the very end is in bounds ...
+        lens2[64] = 0
+        offs[65] = len(c.data)  # ... one byte there is not
+        lens2[65] = 1
+        out.append(replace(c, offsets=offs, caplens=lens2))
+    # snaplen below, at and above the packet sizes
+    for sn in (1, 14, 60, 64, 200, 5000):
+        out.append(make(f"snap{sn}", mix_lens(500, 200, 50), 8, "random", seed=50, snaplen=sn))
+    out.append(make("snap96_1500", np.full(200, 1500), 4, "random", seed=51, snaplen=96))
+    # capacity: all or nothing
+    base = make("cap", np.maximum(mix_lens(700, 300, 60), 1), 8, "some_dropped", seed=60)
+    sp, sb = steered_totals(base)
+    for nm, kw in (("cap_exact", dict(data_cap=sb, max_packets=sp)), ("cap_short1", dict(data_cap=sb - 1)),
+                   ("cap_half", dict(data_cap=sb // 2)), ("cap_zero", dict(data_cap=0)),
+                   ("maxp_short1", dict(max_packets=sp - 1)), ("maxp_zero", dict(max_packets=0)),
+                   ("cap_zero_maxp_zero", dict(max_packets=0, data_cap=0)),
+                   ("index_only", dict(index_only=True)), ("index_only_cap_ignored", dict(index_only=True, data_cap=5)),
+                   ("index_only_maxp_exact", dict(index_only=True, max_packets=sp)),
+                   ("index_only_maxp_short1", dict(index_only=True, max_packets=sp - 1)),
+                   ("no_index", dict(want_index=False)), ("no_index_overflow", dict(want_index=False, data_cap=sb - 1))):
+        out.append(replace(base, name=nm, **kw))
+    names = [c.name for c in out]
+    assert len(set(names)) == len(names)
+    return out
