@@ -1269,7 +1269,9 @@ static void* run_job(void* arg)
 		pcppx_layer scratch[PCPPX_MAX_LAYERS];
 		pcppx_layer* lp = (j->r && j->r->layers && ml) ? j->r->layers + (size_t)i * ml : (ml ? scratch : NULL);
 		pcppx_tuple* tp = (j->r && j->r->tuples) ? &j->r->tuples[i] : NULL;
-		if (j->b->offsets[i] + j->b->caplens[i] > j->b->data_len) {
+		/* out of bounds, or an end that wraps 64 bits (the engine's desc_flags) */
+		if (j->b->offsets[i] + j->b->caplens[i] > j->b->data_len ||
+		    j->b->offsets[i] + j->b->caplens[i] < j->b->offsets[i]) {
 			memset(sp, 0, sizeof(*sp));
 			sp->l4_layer = 0xFF;
 			sp->flags = PCPPX_F_BAD_DESC;

@@ -18,6 +18,8 @@ from pcapplusplus_amd import abi
 FILL = 0xA5
 PAD_BYTES, PAD_ENTRIES = 64, 4
 BLOCK = 1024  # packets per block of the count and copy kernels (pcppx_internal.h kSelectBlockPk)
+BASE_STEP = 256  # block sums per step of select_base_kernel's scan (one wave, four consecutive blocks per lane)
+SCAN3_N = 2 * BASE_STEP * BLOCK + 1029  # two whole steps of that scan, then a block and a partial one
 
 
 @dataclass
@@ -137,13 +139,18 @@ def run_reference(c: Case) -> Buffers:
     return out
 
 
-def run_device(engine, c: Case, device: str = "cuda:0") -> Buffers:
+def run_device(engine, c: Case, device: str = "cuda:0", source=None) -> Buffers:
+    """source: (data, offsets, caplens, data_len) tensors already on the device to select from instead of c's own batch
+    (c then holds the rule, the capacities and, for the runners on the host, the same packets in a small buffer)."""
     import torch
 
     host = alloc(c)
     up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
-    data = up(c.data if len(c.data) else np.zeros(1, np.uint8))
-    offsets, caplens = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32))
+    if source is None:
+        data = up(c.data if len(c.data) else np.zeros(1, np.uint8))
+        offsets, caplens, data_len = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32)), c.dlen()
+    else:
+        data, offsets, caplens, data_len = source
     rule = np.ascontiguousarray(c.keep if c.keep is not None else c.flags)
     rule_t = up(rule if len(rule) else np.zeros(16, np.uint8))
     mis = c.out_misalign
@@ -156,7 +163,7 @@ def run_device(engine, c: Case, device: str = "cuda:0") -> Buffers:
     d_tot = up(host.totals.view(np.int64))
     engine.select_device(data, offsets, caplens, c.n, 1, _spec(c, abi.ptr(rule_t), abi.ptr(rule_t)), d_off, d_cap,
                          d_tot, c.maxp(), d_data, c.cap(), d_idx, torch.cuda.current_stream(device).cuda_stream,
-                         data_len=c.dlen())
+                         data_len=data_len)
     torch.cuda.synchronize(device)
     if d_raw is not None:  # the bytes in front of out->data belong to someone else
         assert bool((d_raw[:16 + mis] == FILL).all()), "bytes before out->data were written"
@@ -230,10 +237,12 @@ def selected_totals(c: Case):
 def cases() -> list[Case]:
     out: list[Case] = []
     # n: the tile and block edges, and 42 / 91 blocks for the block-base scan (one wave, four consecutive blocks per lane:
-    # 23 lanes carry into each other at 91). Its second 256-block step lies beyond the 100k-packet cap of this suite:
-    # tools/bench_select.py checks the keep-everything output against the source at 10M packets (39 steps).
+    # 23 lanes carry into each other at 91). scan3 (1-8 B packets, so half a million of them stay small in bytes) runs the
+    # scan through two whole 256-block steps and a partial third one; tests/test_wide_offsets.py goes on to dozens of
+    # steps with an output past 2^32.
     for n in (0, 1, 63, 64, 65, 255, 256, 257, BLOCK - 1, BLOCK, BLOCK + 1, 2 * BLOCK + 1, 41 * BLOCK + 7, 90 * BLOCK + 5):
         out.append(make(f"n{n}", mix_lens(n, 40, n), "p50", seed=n))
+    out.append(make("scan3", np.random.default_rng(12).integers(1, 9, SCAN3_N).astype(np.uint32), "p50", seed=12))
     out.append(make("n_big_p1", mix_lens(90 * BLOCK + 5, 40, 9), "p1", seed=9))
     out.append(make("n_big_all", mix_lens(66 * BLOCK + 3, 90, 10), "all", seed=10))
     # keep patterns

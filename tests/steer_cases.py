@@ -14,7 +14,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from pcapplusplus_amd import abi
-from select_cases import FILL, PAD_BYTES, PAD_ENTRIES, mix_lens, packed
+from select_cases import FILL, PAD_BYTES, PAD_ENTRIES, SCAN3_N, mix_lens, packed
 
 BLOCK = 1024    # packets per block of the count and copy kernels (pcppx_internal.h kSteerBlockPk)
 SCAN_STEP = 64  # block sums per step of the per-bucket scan (pcppx_internal.h kSteerScanStep)
@@ -164,17 +164,24 @@ def run_reference(c: Case) -> Buffers:
 class DeviceRun:
     """A case's tensors on the device; launch() queues pcppx_steer_device on a stream, result() reads the buffers."""
 
-    def __init__(self, c: Case, device: str = "cuda:0"):
+    def __init__(self, c: Case, device: str = "cuda:0", source=None):
+        """source: (data, offsets, caplens, data_len) tensors already on the device to steer from instead of c's own
+        batch (c then holds the rule, the capacities and, for the runners on the host, the same packets in a small
+        buffer)."""
         import torch
 
         self.c, self.device = c, device
         host = alloc(c)
         up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
-        src = c.data if len(c.data) else np.zeros(1, np.uint8)
-        self.s_raw = up(np.concatenate([np.zeros(16 + c.src_misalign, np.uint8), src]))
-        self.data = self.s_raw[16 + c.src_misalign:]
-        assert self.data.data_ptr() % 16 == c.src_misalign
-        self.offsets, self.caplens = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32))
+        if source is None:
+            src = c.data if len(c.data) else np.zeros(1, np.uint8)
+            self.s_raw = up(np.concatenate([np.zeros(16 + c.src_misalign, np.uint8), src]))
+            self.data = self.s_raw[16 + c.src_misalign:]
+            assert self.data.data_ptr() % 16 == c.src_misalign
+            self.offsets, self.caplens = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32))
+            self.data_len = c.dlen()
+        else:
+            self.data, self.offsets, self.caplens, self.data_len = source
         self.rule = up(_rule(c))
         mis = c.out_misalign
         self.d_raw = None if c.index_only else up(np.concatenate([np.full(16 + mis, FILL, np.uint8), host.data]))
@@ -190,7 +197,7 @@ class DeviceRun:
         c = self.c
         engine.steer_device(self.data, self.offsets, self.caplens, c.n, 1, _spec(c, abi.ptr(self.rule)), self.d_off,
                             self.d_cap, self.d_first, self.d_pos, self.d_tot, c.maxp(), self.d_data, c.cap(), self.d_idx,
-                            stream, data_len=c.dlen())
+                            stream, data_len=self.data_len)
 
     def result(self) -> Buffers:
         import torch
@@ -205,10 +212,10 @@ class DeviceRun:
                        dn(self.d_first, np.uint32), dn(self.d_pos, np.uint64), dn(self.d_tot, np.uint64))
 
 
-def run_device(engine, c: Case, device: str = "cuda:0") -> Buffers:
+def run_device(engine, c: Case, device: str = "cuda:0", source=None) -> Buffers:
     import torch
 
-    run = DeviceRun(c, device)
+    run = DeviceRun(c, device, source)
     run.launch(engine, torch.cuda.current_stream(device).cuda_stream)
     return run.result()
 
@@ -322,6 +329,12 @@ def cases() -> list[Case]:
     offs = c.offsets.copy()
     offs[3::997] = np.uint64(len(c.data))  # bad descriptors in many blocks (every length is >= 1)
     out.append(with_keys(replace(c, offsets=offs), np.random.default_rng(13).integers(0, 1 << 32, c.n), 16, 4))
+    # the n of select_cases' scan3 (513 blocks and a partial one): nine steps of the per-bucket scan and of the dropped /
+    # bad sums, with dropped and bad packets in every step
+    c = make("scan3_k2_drops_bad", small_lens(SCAN3_N, 14), 2, "some_dropped", seed=14)
+    offs = c.offsets.copy()
+    offs[3::997] = np.uint64(len(c.data))
+    out.append(replace(c, offsets=offs))
     # K
     for K in (1, 2, 3, 7, 8, 64, 255, 256):
         out.append(make(f"k{K}", mix_lens(1500, 100, K), K, "random", seed=K))

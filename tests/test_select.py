@@ -41,8 +41,12 @@ def test_cases_cover_the_kernel_shapes():
     txt = (abi.PKG_DIR / "csrc" / "pcppx_internal.h").read_text()
     assert int(re.search(r"kSelectBlockPk\s*=\s*(\d+)", txt).group(1)) == sc.BLOCK
     by = {c.name: c for c in CASES}
-    assert max(c.n for c in CASES) <= 100_000
+    assert max(c.n for c in CASES if c.name != "scan3") <= 100_000
     assert by[f"n{90 * sc.BLOCK + 5}"].n > 64 * sc.BLOCK  # more blocks than a wave has lanes
+    assert re.search(r"\(256 per step", (abi.PKG_DIR / "csrc" / "pcppx_select.hip").read_text()) and sc.BASE_STEP == 256
+    s3 = by["scan3"]  # the base scan's third step, a kept packet in it, and a batch that stays small in bytes
+    assert s3.n == 2 * sc.BASE_STEP * sc.BLOCK + 1029 and -(-s3.n // sc.BLOCK) > 2 * sc.BASE_STEP
+    assert 1 <= int(s3.caplens.min()) and int(s3.caplens.max()) <= 8 and s3.keep[2 * sc.BASE_STEP * sc.BLOCK:].any()
     t = sc.brute(by["cap_short1"]).totals
     sp, sb = sc.selected_totals(by["cap_exact"])  # the totals with room for everything
     assert int(t[abi.SEL_WRITTEN_PACKETS]) == sp - 1 and int(t[abi.SEL_SELECTED_PACKETS]) == sp

@@ -54,8 +54,15 @@ def test_cases_cover_the_kernel_shapes():
     txt = (abi.PKG_DIR / "csrc" / "pcppx_internal.h").read_text()
     assert int(re.search(r"kSteerBlockPk\s*=\s*(\d+)", txt).group(1)) == tc.BLOCK
     assert int(re.search(r"kSteerScanStep\s*=\s*(\d+)", txt).group(1)) == tc.SCAN_STEP
-    assert max(c.n for c in CASES) <= 100_000
+    assert max(c.n for c in CASES if not c.name.startswith("scan3")) <= 100_000
     blocks = lambda c: -(-c.n // tc.BLOCK)  # noqa: E731
+    s3 = BY_NAME["scan3_k2_drops_bad"]  # more than two steps of the dropped / bad sums, with something to sum in each
+    assert s3.n_buckets == 2 and blocks(s3) > 2 * 256 > 2 * tc.SCAN_STEP and int(s3.caplens.max()) <= 8
+    t = tc.brute(s3).totals
+    assert int(t[abi.STEER_DROPPED]) > blocks(s3) and int(t[abi.STEER_BAD_DESC]) > blocks(s3) // 4
+    for lo in range(0, s3.n, tc.SCAN_STEP * tc.BLOCK):
+        step = slice(lo, lo + tc.SCAN_STEP * tc.BLOCK)
+        assert (s3.buckets()[step] >= 2).any() and (s3.offsets[step] == len(s3.data)).any()
     big = [c for c in CASES if c.name.startswith("big_")]
     assert all(blocks(c) > tc.SCAN_STEP for c in big)  # a second step of the per-bucket scan and of the block sums
     assert any(c.n_buckets > 3 * tc.BUCKET_STEP for c in big)  # four steps of the bucket-base scan
