@@ -224,7 +224,7 @@ __device__ __forceinline__ bool sip_key(uint32_t k)
 	return ((kSip.valid >> h) & 1u) && kSip.key[h] == k;
 }
 
-// Round 6: the same trigger sets as register tables for the fast path (ParseShape R6 bit 2). A perfect hash of the port
+// Round 6: the same trigger sets as register tables for the fast path (l7_pre_regs). A perfect hash of the port
 // (one 24-bit multiply and a bit-field extract; multipliers found by search, collision-freedom asserted below) picks a
 // slot; the lane holding that slot of a table register hands its entry over by ds_bpermute -- an LDS-crossbar op, no
 // memory round trip per packet. TCP: 64 slots, entry = port | 0x10000. UDP: slots 0-31 of the second register, entry =
@@ -1374,20 +1374,16 @@ __device__ __forceinline__ uint32_t fnv4(uint32_t h, uint32_t v)
 // Byte sequences: [port_a port_b ip_a ip_b proto] and [ip_a ip_b], the pair ordered as the reference
 // orders it (raw-order port compare, then LE u32 (IPv4) / memcmp (IPv6) address compare).
 // The address dwords past the first (IPv6) are hashed under a select, not a branch: a wave mixing IPv4 and IPv6 lanes
-// runs them either way, and the selects spare the exec-mask bookkeeping of 24 branches (kBranchy: the branches, a
-// tools-only diagnostic).
-// kV4Skip (R6 bit 3): the address dwords past the first are hashed only when some active lane hashes an IPv6 pair (a
-// wave-uniform branch on a ballot): a wave of IPv4 packets runs 3 x 2-3 dword steps instead of 3 x 8-9.
-template <bool kBranchy = false, bool kV4Skip = false>
+// runs them either way, and the selects spare the exec-mask bookkeeping of 24 branches.
+// The address dwords past the first are hashed only when some active lane hashes an IPv6 pair (a wave-uniform branch on
+// a ballot): a wave of IPv4 packets runs 3 x 2-3 dword steps instead of 3 x 8-9.
 __device__ __forceinline__ void tuple_hashes(const uint32_t (&s)[4], const uint32_t (&d)[4], uint32_t na, bool has_l4,
                                              uint32_t pw, uint32_t proto, uint32_t& h5, uint32_t& h5d, uint32_t& h2)
 {
-	const bool any6 = !kV4Skip || __ballot(na != 1) != 0;  // uniform over the active lanes
+	const bool any6 = __ballot(na != 1) != 0;  // uniform over the active lanes
 	auto add4 = [&](uint32_t h, uint32_t k, uint32_t v) -> uint32_t {
 		if (k > 0 && !any6)
 			return h;
-		if (kBranchy)
-			return k < na ? fnv4(h, v) : h;
 		const uint32_t y = fnv4(h, v);
 		return k < na ? y : h;
 	};
@@ -1437,7 +1433,6 @@ __device__ __forceinline__ void tuple_hashes(const uint32_t (&s)[4], const uint3
 // hash5Tuple / hash2Tuple of a generic-walk packet: addresses of the first IPv4 (else first IPv6) layer,
 // ports of the last TCP (else last UDP) layer, the IP layer's protocol / next-header byte. Dword reads
 // from the LDS window where the bytes are staged (rd32), else from HBM.
-template <bool kV4Skip = false>
 __device__ __forceinline__ void hashes(const Pkt& p, const Walk& w, uint32_t& h5, uint32_t& h5d, uint32_t& h2)
 {
 	h5 = h5d = h2 = 0;
@@ -1456,154 +1451,7 @@ __device__ __forceinline__ void hashes(const Pkt& p, const Walk& w, uint32_t& h5
 	}
 	const bool has_l4 = w.l4i >= 0 && !(w.mask & (1ull << P_ICMP));  // ICMP: no 5-tuple (PacketUtils.cpp:144-145)
 	const uint32_t pw = has_l4 ? rd32(p, w.l4o) : 0;
-	tuple_hashes<false, kV4Skip>(s, d, na, has_l4, pw, rb(p, ipo + (v4 ? 9 : 6)), h5, h5d, h2);
-}
-
-// ---- the three hashes of a whole wave (round 6, ParseShape R6 bit 1) ----
-// A packet's hash inputs, gathered by whichever walk parsed it: the first IPv4 (else first IPv6) layer's addresses (na
-// dwords each, zero past na: also the 5-tuple extract's address fields), the port layer's raw port dword (pw, whenever a
-// TCP / UDP layer exists), and meta = IP protocol / next-header byte | IPv4 << 8 | IPv6 << 9 | hashed ports << 10 (a port
-// layer, an IP layer and no ICMP, PacketUtils.cpp:141-148) | a port layer << 11.
-struct HashIn
-{
-	uint32_t s[4], d[4], pw, meta;
-};
-__device__ __forceinline__ HashIn hash_in_none()
-{
-	HashIn h;
-#pragma unroll
-	for (int k = 0; k < 4; ++k)
-		h.s[k] = h.d[k] = 0;
-	h.pw = h.meta = 0;
-	return h;
-}
-// the inputs hashes() reads, from the LDS window where staged, else HBM (a generic-walk packet)
-__device__ __forceinline__ HashIn hash_in_walk(const Pkt& p, const Walk& w)
-{
-	HashIn h = hash_in_none();
-	const bool v4 = w.v4 >= 0, ip = v4 || w.v6 >= 0;
-	const uint32_t ipo = v4 ? (uint32_t)w.v4 : (uint32_t)w.v6;
-	const uint32_t na = ip ? (v4 ? 1u : 4u) : 0u;
-	const uint32_t so = ipo + (v4 ? 12 : 8), dofs = ipo + (v4 ? 16 : 24);
-#pragma unroll
-	for (int k = 0; k < 4; ++k)
-	{
-		h.s[k] = (uint32_t)k < na ? rd32(p, so + 4 * k) : 0u;
-		h.d[k] = (uint32_t)k < na ? rd32(p, dofs + 4 * k) : 0u;
-	}
-	const bool l4 = w.l4i >= 0;
-	const bool has5 = l4 && !(w.mask & (1ull << P_ICMP));
-	h.pw = l4 ? rd32(p, w.l4o) : 0u;
-	h.meta = (ip ? (rb(p, ipo + (v4 ? 9 : 6)) | (v4 ? 0x100u : 0x200u) | (has5 ? 0x400u : 0u)) : 0u) | (l4 ? 0x800u : 0u);
-	return h;
-}
-// hash5Tuple (both directions) and hash2Tuple (PacketUtils.cpp:114-245) of every lane's packet, all 64 lanes together
-// (call with the wave converged). The byte sequences are tuple_hashes': [ports addr_a addr_b proto] and [addr_a addr_b].
-// IPv4 packets hash their 3 x 13 / 8 bytes in their own lanes. An IPv6 packet's chains are 37 / 37 / 32 bytes: run in its
-// own lane they would hold every lane of a mixed wave for them, so each IPv6 chain goes to a lane of its own instead --
-// chain k of the r-th IPv6 packet to slot k * n6 + r (k: 0 hash2Tuple, 1 hash5Tuple direction-unique, 2 hash5Tuple with
-// the pair swapped, needed only when the reference swaps it), 64 slots per round, the inputs and results moved by
-// ds_bpermute. `own`: 64 words of LDS scratch (the rank -> lane map).
-__device__ __forceinline__ void wave_tuple_hashes(const HashIn& x, uint32_t* own, uint32_t& h5, uint32_t& h5d, uint32_t& h2)
-{
-	const uint32_t lane = threadIdx.x & 63u;
-	const bool v4 = x.meta & 0x100u, v6 = x.meta & 0x200u, l4 = x.meta & 0x400u;
-	const uint32_t proto = x.meta & 0xFFu;
-	// the address order: dst <=> src as LE u32 (IPv4) / memcmp(dst, src) (IPv6)
-	int cmp = x.d[0] < x.s[0] ? -1 : (x.d[0] > x.s[0] ? 1 : 0);
-	if (!v4)
-	{
-		cmp = 0;
-#pragma unroll
-		for (int k = 3; k >= 0; --k)
-		{
-			const uint32_t a = __builtin_bswap32(x.d[k]), b = __builtin_bswap32(x.s[k]);
-			cmp = a < b ? -1 : (a > b ? 1 : cmp);
-		}
-	}
-	const bool sw2 = cmp < 0;
-	const uint32_t sp = x.pw & 0xFFFF, dp = x.pw >> 16;  // raw network-order values, LE-loaded
-	const bool swap = dp < sp || (dp == sp && cmp < 0);
-	constexpr uint32_t iv = 2166136261u;
-	h2 = h5 = h5d = 0;
-	if (__ballot(v4))  // uniform
-	{
-		const uint32_t a = sw2 ? x.d[0] : x.s[0], b = sw2 ? x.s[0] : x.d[0];
-		const uint32_t y2 = fnv4(fnv4(iv, a), b);
-		const uint32_t yd = fnv(fnv4(fnv4(fnv4(iv, x.pw), x.s[0]), x.d[0]), proto);
-		uint32_t ys = yd;
-		if (__ballot(v4 && l4 && swap))  // uniform
-		{
-			const uint32_t t = fnv(fnv4(fnv4(fnv4(iv, (x.pw >> 16) | (x.pw << 16)), x.d[0]), x.s[0]), proto);
-			ys = swap ? t : yd;
-		}
-		h2 = v4 ? y2 : 0u;
-		h5d = v4 && l4 ? yd : 0u;
-		h5 = v4 && l4 ? ys : 0u;
-	}
-	const uint64_t m6 = __ballot(v6);
-	if (m6)  // uniform
-	{
-		const uint32_t n6 = (uint32_t)__popcll(m6);
-		const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m6 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m6, 0u));
-		if (v6)
-			own[rank] = lane;
-		__syncthreads();  // one wave per block: orders the map's writes before its reads
-		const uint32_t fl = proto | (sw2 ? 0x100u : 0u);
-		uint32_t r0 = 0, r1 = 0, r2 = 0;
-		for (uint32_t base = 0; base < 3 * n6; base += 64)  // uniform
-		{
-			const uint32_t t = base + lane;
-			const uint32_t k = t >= 2 * n6 ? 2u : (t >= n6 ? 1u : 0u);
-			const uint32_t o = own[(t - k * n6) & 63u];
-			uint32_t S[4], D[4];
-#pragma unroll
-			for (int j = 0; j < 4; ++j)
-			{
-				S[j] = __shfl(x.s[j], (int)o, 64);
-				D[j] = __shfl(x.d[j], (int)o, 64);
-			}
-			const uint32_t pw = __shfl(x.pw, (int)o, 64), of = __shfl(fl, (int)o, 64);
-			const bool dfirst = k == 2 || (k == 0 && (of & 0x100u));
-			const uint32_t yp = fnv4(iv, k == 2 ? (pw >> 16) | (pw << 16) : pw);
-			uint32_t y = k ? yp : iv;
-#pragma unroll
-			for (int j = 0; j < 4; ++j)
-				y = fnv4(y, dfirst ? D[j] : S[j]);
-#pragma unroll
-			for (int j = 0; j < 4; ++j)
-				y = fnv4(y, dfirst ? S[j] : D[j]);
-			const uint32_t yq = fnv(y, of & 0xFFu);
-			y = k ? yq : y;
-			// each owner takes its chains' results from the slots of this round
-			const uint32_t q0 = rank, q1 = n6 + rank, q2 = 2 * n6 + rank;
-			const uint32_t g0 = __shfl(y, (int)(q0 & 63u), 64), g1 = __shfl(y, (int)(q1 & 63u), 64),
-			               g2 = __shfl(y, (int)(q2 & 63u), 64);
-			r0 = (q0 >= base && q0 < base + 64) ? g0 : r0;
-			r1 = (q1 >= base && q1 < base + 64) ? g1 : r1;
-			r2 = (q2 >= base && q2 < base + 64) ? g2 : r2;
-		}
-		if (v6)
-		{
-			h2 = r0;
-			h5d = l4 ? r1 : 0u;
-			h5 = l4 ? (swap ? r2 : r1) : 0u;
-		}
-	}
-}
-
-// write_tuple from the inputs the hashes used (the same bytes: the fields hash5Tuple reads)
-__device__ __forceinline__ void write_tuple_in(const HashIn& x, const Walk& w, uint32_t h5, pcppx_tuple* out)
-{
-	const bool ip = (x.meta & 0x300u) != 0, l4 = (x.meta & 0x800u) != 0;
-	const uint32_t ports = swap16(x.pw) | (swap16(x.pw >> 16) << 16);  // getSrcPort / getDstPort (host order)
-	const bool has5 = (x.meta & 0x400u) != 0;
-	const uint32_t meta = (ip ? ((x.meta & 0x100u) ? 4u : 6u) : 0u) | ((x.meta & 0xFFu) << 8) |
-	                      ((l4 ? (w.is_tcp ? P_TCP : P_UDP) : 0u) << 16) | ((has5 ? 1u : 0u) << 24);
-	uint4* o = reinterpret_cast<uint4*>(out);
-	o[0] = make_uint4(x.s[0], x.s[1], x.s[2], x.s[3]);
-	o[1] = make_uint4(x.d[0], x.d[1], x.d[2], x.d[3]);
-	o[2] = make_uint4(ports, meta, h5, (w.flags & 0xFFFFu) | ((w.n_layers & 0xFFu) << 16));
+	tuple_hashes(s, d, na, has_l4, pw, rb(p, ipo + (v4 ? 9 : 6)), h5, h5d, h2);
 }
 
 // IPv4 header checksum (IPv4Layer.cpp:410-412): computeChecksum over min(IHL*4, dataLen) header bytes
@@ -1660,16 +1508,6 @@ __device__ __forceinline__ uint32_t l4_checksum(const Pkt& p, const Walk& w, uin
 	uint32_t fw, ph;
 	l4_inputs(p, w, &fw, &ph);
 	return l4_checksum_from(w, l4_residue, fw, ph, stored);
-}
-
-__device__ __forceinline__ void write_summary(pcppx_summary* out, uint32_t h5, uint32_t h5d, uint32_t h2,
-                                              uint32_t flags, uint32_t n_layers, int32_t l4i, uint64_t mask,
-                                              uint32_t ipc, uint32_t ips, uint32_t l4c, uint32_t l4s)
-{
-	uint4 s0 = make_uint4(h5, h5d, h2, flags | (n_layers << 16) | ((l4i >= 0 ? (uint32_t)l4i : 0xFFu) << 24));
-	uint4 s1 = make_uint4((uint32_t)mask, (uint32_t)(mask >> 32), ipc | (ips << 16), l4c | (l4s << 16));
-	reinterpret_cast<uint4*>(out)[0] = s0;
-	reinterpret_cast<uint4*>(out)[1] = s1;
 }
 
 // the 5-tuple extract (pcppx_tuple): the fields hash5Tuple reads (PacketUtils.cpp:139-210) -- the first IPv4, else first
@@ -1925,32 +1763,12 @@ __device__ __forceinline__ bool fast_walk(const Pkt& p, uint32_t cap, const Para
 }
 
 // The table words the L7 trigger of a fast-path packet needs (tcp_l7 / udp_l7 / sip_key: port bitmap words and the
-// SIP key slot), loaded ahead of the hashes so that their latency hides behind them (fast_l7 consumes them).
+// SIP key slot), looked up ahead of the hashes (fast_l7 consumes them).
 struct L7Pre
 {
 	uint32_t ws, wd, wu, sk;  // src / dst port words of the TCP or UDP bitmap, dst word of udp_dst, SIP slot key
 };
-__device__ __forceinline__ L7Pre fast_l7_pre(const Pkt& p, const Fast& f)
-{
-	L7Pre r{ 0u, 0u, 0u, 0u };
-	if (f.payload() && f.l4())
-	{
-		const uint32_t pw = lds_u32(p, f.l4o());
-		const uint32_t sport = swap16(pw), dport = swap16(pw >> 16);
-		const uint32_t* t = f.tcp() ? kL7.tcp : kL7.udp;
-		r.ws = t[sport >> 5];
-		r.wd = t[dport >> 5];
-		if (!f.tcp())
-		{
-			r.wu = kL7.udp_dst[dport >> 5];
-			if (f.l4dlen() - 8 >= 4)  // the SIP heuristic's 4 payload bytes (in the window: fast_walk)
-				r.sk = kSip.key[(__builtin_bswap32(lds_u32(p, f.l4o() + 8)) * kSipMul) >> 27];
-		}
-	}
-	return r;
-}
-
-// fast_l7_pre's words from the register tables (kL7R, R6 bit 2): called by every lane of the wave (ds_bpermute reads the
+// L7Pre's words from the register tables (kL7R): called by every lane of the wave (ds_bpermute reads the
 // table registers of all 64 lanes), `on` for the fast-path packets with a payload behind their TCP / UDP layer. Each
 // word holds only the bit fast_l7 tests (a port's bit of its 32-port group), the SIP slot's key as kSip.key holds it.
 __device__ __forceinline__ L7Pre l7_pre_regs(const Pkt& p, const Fast& f, bool on, uint32_t rt, uint32_t rus)
@@ -1980,7 +1798,7 @@ __device__ __forceinline__ L7Pre l7_pre_regs(const Pkt& p, const Fast& f, bool o
 }
 
 // L7 dispatch of a fast-path packet (same rules as walk_chain's): an L7 payload ends the chain after the
-// L4 layer, with no Payload and no trailer. `pre`: fast_l7_pre's words (the same tests as tcp_l7 / udp_l7 / sip_key)
+// L4 layer, with no Payload and no trailer. `pre`: l7_pre_regs' words (the same tests as tcp_l7 / udp_l7 / sip_key)
 __device__ __forceinline__ void fast_l7(const Pkt& p, Fast& f, uint32_t cap, const L7Pre& pre)
 {
 	const bool payload = f.payload() != 0, tcp = f.tcp() != 0;
@@ -2099,30 +1917,8 @@ __device__ __forceinline__ void fast_emit(const Fast& f, uint32_t cap, uint32_t 
 	emit(tl != 0, P_TRAILER, 2, lasto + lastd, tl, tl);
 }
 
-// the same inputs of a fast-path packet: every byte in the LDS window
-__device__ __forceinline__ HashIn hash_in_fast(const Pkt& p, const Fast& f, const Walk& w)
-{
-	HashIn h;
-	const bool v4 = w.v4 >= 0;
-	const uint32_t ipo = v4 ? (uint32_t)w.v4 : (uint32_t)w.v6;
-	const uint32_t na = v4 ? 1 : 4;
-	const uint32_t so = ipo + (v4 ? 12 : 8), dofs = ipo + (v4 ? 16 : 24);
-#pragma unroll
-	for (int k = 0; k < 4; ++k)
-	{
-		h.s[k] = (uint32_t)k < na ? lds_u32(p, so + 4 * k) : 0u;
-		h.d[k] = (uint32_t)k < na ? lds_u32(p, dofs + 4 * k) : 0u;
-	}
-	const uint32_t proto = (lds_u32(p, ipo + (v4 ? 8 : 4)) >> (v4 ? 8 : 16)) & 0xFF;
-	const bool l4 = f.l4() != 0;  // TCP / UDP only: no ICMP on the fast path
-	h.pw = l4 ? lds_u32(p, f.l4o()) : 0u;
-	h.meta = proto | (v4 ? 0x100u : 0x200u) | (l4 ? 0xC00u : 0u);
-	return h;
-}
-
 // hash5Tuple x2 + hash2Tuple of a fast-path packet (every byte in the LDS window): the first IPv4 (else the first
 // IPv6) layer's addresses and protocol / next-header byte, the L4 layer's ports
-template <bool kBranchy = false, bool kV4Skip = false>
 __device__ __forceinline__ void fast_hashes(const Pkt& p, const Fast& f, const Walk& w, uint32_t& h5, uint32_t& h5d,
                                             uint32_t& h2)
 {
@@ -2138,7 +1934,7 @@ __device__ __forceinline__ void fast_hashes(const Pkt& p, const Fast& f, const W
 		d[k] = (uint32_t)k < na ? lds_u32(p, dofs + 4 * k) : 0;
 	}
 	const uint32_t proto = (lds_u32(p, ipo + (v4 ? 8 : 4)) >> (v4 ? 8 : 16)) & 0xFF;
-	tuple_hashes<kBranchy, kV4Skip>(s, d, na, f.l4() != 0, lds_u32(p, f.l4o()), proto, h5, h5d, h2);
+	tuple_hashes(s, d, na, f.l4() != 0, lds_u32(p, f.l4o()), proto, h5, h5d, h2);
 }
 
 // IPv4 header checksum of the first IPv4 layer, from dword reads of the (fully staged) header
@@ -2305,21 +2101,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x)
 	return x;
 }
 
-// min / max / sum of one value per lane by DPP (row_shr 1/2/4/8 inside 16-lane rows, then the row broadcasts): lane 63
-// ends with the whole wave's, read into an SGPR -- no LDS round trips (the ds_bpermute butterflies of wave_min_u64 & co.
-// wait on LDS at every one of their six steps)
-template <class Op>
-__device__ __forceinline__ uint32_t wave_reduce_dpp(uint32_t x, uint32_t ident, Op op)
-{
-	x = op(x, (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, 0x111, 0xF, 0xF, false));  // row_shr:1
-	x = op(x, (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, 0x112, 0xF, 0xF, false));  // row_shr:2
-	x = op(x, (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, 0x114, 0xF, 0xF, false));  // row_shr:4
-	x = op(x, (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, 0x118, 0xF, 0xF, false));  // row_shr:8
-	x = op(x, (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, 0x142, 0xA, 0xF, false));  // row_bcast:15
-	x = op(x, (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, 0x143, 0xC, 0xF, false));  // row_bcast:31
-	return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
-
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
 {
 	for (int m = 32; m >= 1; m >>= 1)
@@ -2443,43 +2224,40 @@ __device__ __forceinline__ uint32_t deep_extent(const Pkt& p, uint32_t et, uint3
 
 constexpr uint32_t kRowMaxMl = 12;  // layer rows staged in LDS up to this max_layers; beyond, direct stores
 
-// The shape switches of one parse_tile_kernel instance. The product instances use ParseShape<> (below: only the
-// checksum instance of PCPPX_WINDOW_DEEP differs, in EarlyB); the diagnostics exist for tools/ab/libpcppx_ab.so only.
-//   NT: non-temporal record stores (write-once data; profiles/r01_ab_nontemporal.txt); the span-stream loads use the
-//     default policy since round 4 (their lines are the ones the header gather reads too: config 3 -1.7%,
-//     profiles/r04k_ab_cfg3.txt)
-//   FillTails: the staged FIXED layer rows are zero-filled past n_layers and stored whole: full-line stores, 3.5% faster
-//     on config 3 than storing only the chain's records (profiles/r02_ab_tails.txt)
-//   TightR2: the second gather round reads only up to the deep stack's header extent (deep_extent) instead of the whole
-//     window (profiles/r02_ab_tight_r2.txt)
-//   Realign: a deep stack that ends past the window is re-gathered from a dword-aligned start (mis <= 3 instead of <= 15)
-//     so that it fits (profiles/r02_ab_realign.txt)
+// The shape of one parse_tile_kernel instance beyond its window sizes. The product instances use ParseShape<> (below:
+// only the checksum instance of PCPPX_WINDOW_DEEP differs, in EarlyB); the diagnostics exist for
+// tools/ab/libpcppx_ab.so only, one per instance.
 //   EarlyB: the second span-stream window is issued with the first, before the header gather (0.8-0.9% on config 3,
 //     profiles/r03_ab_earlyB_*.txt)
-//   diagnostics (wrong or marked records; static_assert'ed out of libpcppx.so): StreamOnly (no header gather / parse;
-//     L4 range = [14, caplen)), MarkFast (flags bit 0x8000 on the packets the fast path took), GatherOnly (descriptors,
-//     both gather rounds for every packet and the record stores, no parse: the memory time of the access pattern),
-//     SkipGeneric (packets off the fast path are not walked: the time the generic walk costs), Skip (a fast-path stage
-//     left out, for its cost: bit 0 the hashes, bit 1 the L7 decision, bit 2 the layer rows; bit 3: the L7 table reads
-//     after the hashes instead of before; bit 4: non-temporal span-stream loads (rounds 1-3) instead of default-policy
-//     ones; bit 5:
-//     the IPv6 address dwords hashed under branches instead of selects; records unchanged by bits 3-5; bit 6: only the
-//     first half of a PACKED run stored)
-//   R6 (round 6, records unchanged by every bit): bit 0 the tile span from 32-bit DPP reductions (wave_reduce_dpp)
-//     instead of 64-bit ds_bpermute butterflies; bit 1 the three hashes taken by the whole wave after both walks
-//     (wave_tuple_hashes: IPv4 packets in their own lanes, IPv6 packets' chains spread over the wave's lanes); bit 2 the
-//     L7 trigger ports looked up in register tables by ds_bpermute (l7_pre_regs) instead of constant-memory bitmaps;
-//     bit 3 (with bit 1 off) the per-lane hashes skip the IPv6 address dwords in waves of IPv4 packets (tuple_hashes);
-//     bit 4 the span stream issues no window loads past the tile's last window
-template <bool kNT = true, bool kFillTails = true, bool kTightR2 = true, bool kRealign = true, bool kEarlyB = true,
-          bool kStreamOnly = false, bool kMarkFast = false, bool kGatherOnly = false, bool kSkipGeneric = false,
-          int kSkip = 0, int kR6 = 28>
+//   Diag (wrong or marked records; static_assert'ed out of libpcppx.so):
+//     StreamOnly: no header gather / parse; L4 range = [14, caplen)
+//     GatherOnly: descriptors, both gather rounds for every packet and the record stores, no parse: the memory time of
+//       the access pattern
+//     MarkFast: flags bit 0x8000 on the packets the fast path took
+//     HalfPacked: only the first half of a PACKED run stored (the time's sensitivity to the row bytes)
+// Settled switches, now simply the kernel (their other legs: git history):
+//   NT, non-temporal record stores; span-stream loads default-policy: profiles/r01_ab_nontemporal.txt, r04k_ab_cfg3.txt
+//   FillTails, staged FIXED rows zero-filled and stored whole: profiles/r02_ab_tails.txt
+//   TightR2, the second gather round only up to the deep stack's header extent: profiles/r02_ab_tight_r2.txt
+//   Realign, a deep stack past the window re-gathered from a dword-aligned start: profiles/r02_ab_realign.txt
+//   SkipGeneric, packets off the fast path not walked (diagnostic): profiles/r02_ab_skip_generic.txt
+//   Skip bits 0-2, a fast-path stage left out for its cost (diagnostic): profiles/r05l_ab_cfg3s64_stages.txt
+//   Skip bits 3-5, L7 table reads after the hashes / NT stream loads / hashes under branches: profiles/r04k_ab_cfg*.txt
+//   R6 bits 0-1, DPP span reductions / wave-wide hashes, rejected: profiles/r06{a,b,c}_ab6_cfg*.txt
+//   R6 bits 2-4, L7 register tables / IPv4-wave hash skip / no padded stream loads, kept: profiles/r06{c,e,f}_ab6_cfg*.txt
+enum class ParseDiag
+{
+	None,
+	StreamOnly,
+	GatherOnly,
+	MarkFast,
+	HalfPacked
+};
+template <bool kEarlyB = true, ParseDiag kDiag = ParseDiag::None>
 struct ParseShape
 {
-	static constexpr bool NT = kNT, FillTails = kFillTails, TightR2 = kTightR2, Realign = kRealign, EarlyB = kEarlyB;
-	static constexpr bool StreamOnly = kStreamOnly, MarkFast = kMarkFast, GatherOnly = kGatherOnly,
-	                      SkipGeneric = kSkipGeneric;
-	static constexpr int Skip = kSkip, R6 = kR6;
+	static constexpr bool EarlyB = kEarlyB;
+	static constexpr ParseDiag Diag = kDiag;
 };
 
 // One wave = one 64-packet tile. MinWaves: __launch_bounds__ minimum waves per SIMD (1 = the compiler's choice).
@@ -2503,14 +2281,13 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	// PCPPX_LAYOUT_PACKED stages a tile's chains (kTile * PCPPX_PACKED_MAX_LAYERS entries) in the stage
 	constexpr bool kPackedOk = kTSlotDw >= 2 * PCPPX_PACKED_MAX_LAYERS;
 #ifndef PCPPX_TOOLS_AB
-	// the diagnostic switches write wrong or marked records: only tools/ab/libpcppx_ab.so (built with PCPPX_TOOLS_AB)
+	// the diagnostics write wrong or marked records: only tools/ab/libpcppx_ab.so (built with PCPPX_TOOLS_AB)
 	// may instantiate them, never libpcppx.so; and every product instance can stage a PACKED run
-	static_assert(!S::MarkFast && !S::GatherOnly && !S::SkipGeneric && !S::StreamOnly && S::Skip == 0,
-	              "tools-only parse_tile_kernel switch");
+	static_assert(S::Diag == ParseDiag::None, "tools-only parse_tile_kernel diagnostic");
 	static_assert(kPackedOk, "a product instance must stage PCPPX_LAYOUT_PACKED rows");
 #endif
-	constexpr bool NT = S::NT, StreamOnly = S::StreamOnly, MarkFast = S::MarkFast, FillTails = S::FillTails,
-	               GatherOnly = S::GatherOnly, SkipGeneric = S::SkipGeneric, TightR2 = S::TightR2, Realign = S::Realign;
+	constexpr bool StreamOnly = S::Diag == ParseDiag::StreamOnly, GatherOnly = S::Diag == ParseDiag::GatherOnly,
+	               MarkFast = S::Diag == ParseDiag::MarkFast, HalfPacked = S::Diag == ParseDiag::HalfPacked;
 	const bool want_csum = Csum && prm.want_csum;  // uniform
 
 	const uint32_t lane = threadIdx.x;
@@ -2521,9 +2298,9 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	bool empty = true;
 	const uint32_t bad = in ? desc_flags(off, cap, prm.data_len, &empty) : 0;
 	const bool live = in && !bad && !empty;
-	// R6 bit 2: this lane's slots of the L7 register tables (one coalesced 256-B read each, issued with the descriptors)
+	// this lane's slots of the L7 register tables (one coalesced 256-B read each, issued with the descriptors)
 	uint32_t l7_rt = 0, l7_rus = 0;
-	if ((S::R6 & 4) && !S::StreamOnly && !S::GatherOnly)
+	if (!StreamOnly && !GatherOnly)
 	{
 		l7_rt = kL7R.tcp[lane];
 		l7_rus = kL7R.udp_sip[lane];
@@ -2533,40 +2310,9 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	// stream window is issued now and lands while the headers are gathered and parsed ----
 	const uint64_t pkt_addr = (uint64_t)(uintptr_t)prm.data + off;
 	// wave reductions are uniform: moved to SGPRs so the window loop is a scalar loop
-	uint64_t smin, emax, wire;
-	if (S::R6 & 1)
-	{
-		// round 6: 32-bit DPP reductions of each packet's span against one live packet's address (wave-uniform), and
-		// of the caplens (<= 65535 each: the tile's sum fits 32 bits). A span that is not within +-2 GiB of that base
-		// cannot stream anyway (emax - smin <= 2 * wire + 64 KiB), so such a tile only skips the reductions.
-		const uint64_t lm = __ballot(live);
-		smin = ~0ull;
-		emax = wire = 0;
-		if (want_csum && lm)  // uniform
-		{
-			const int first = __builtin_ctzll(lm);
-			const uint64_t base = (((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pkt_addr >> 32), first) << 32) |
-			                       (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pkt_addr, first)) & ~15ull;
-			const int64_t d0 = (int64_t)((pkt_addr & ~15ull) - base), d1 = (int64_t)(((pkt_addr + cap + 15) & ~15ull) - base);
-			const bool far = live && (d0 < INT32_MIN || d0 > INT32_MAX || d1 < INT32_MIN || d1 > INT32_MAX);
-			if (!__ballot(far))  // uniform
-			{
-				const int32_t lo = (int32_t)wave_reduce_dpp(live ? (uint32_t)(int32_t)d0 : (uint32_t)INT32_MAX, (uint32_t)INT32_MAX,
-				                                            [](uint32_t a, uint32_t b) { return (int32_t)a < (int32_t)b ? a : b; });
-				const int32_t hi = (int32_t)wave_reduce_dpp(live ? (uint32_t)(int32_t)d1 : (uint32_t)INT32_MIN, (uint32_t)INT32_MIN,
-				                                            [](uint32_t a, uint32_t b) { return (int32_t)a > (int32_t)b ? a : b; });
-				smin = base + (uint64_t)(int64_t)lo;
-				emax = base + (uint64_t)(int64_t)hi;
-				wire = wave_reduce_dpp(live ? cap : 0u, 0u, [](uint32_t a, uint32_t b) { return a + b; });
-			}
-		}
-	}
-	else
-	{
-		smin = uniform_u64(wave_min_u64(live ? (pkt_addr & ~15ull) : ~0ull));
-		emax = uniform_u64(wave_max_u64(live ? ((pkt_addr + cap + 15) & ~15ull) : 0ull));
-		wire = uniform_u64(wave_sum_u64(live ? cap : 0));
-	}
+	const uint64_t smin = uniform_u64(wave_min_u64(live ? (pkt_addr & ~15ull) : ~0ull));
+	const uint64_t emax = uniform_u64(wave_max_u64(live ? ((pkt_addr + cap + 15) & ~15ull) : 0ull));
+	const uint64_t wire = uniform_u64(wave_sum_u64(live ? cap : 0));
 	const bool stream = want_csum && emax > smin && emax - smin <= 2 * wire + 65536;  // uniform
 	const uint32_t nchunks = stream ? (uint32_t)((emax - smin) >> 4) : 0;
 	uint4 va[SWin / 64], vb[SWin / 64];
@@ -2577,14 +2323,7 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 			// clamped, not masked: lanes past the span re-read its last chunk (same line, no extra
 			// traffic); their values lie after every prefix target, so they are inert
 			const uint32_t c = win * SWin + 64 * k + lane;
-			const uintptr_t a = smin + 16ull * (c < nchunks ? c : nchunks - 1);
-			if (NT && (S::Skip & 16))  // diagnostic: the round 1-3 non-temporal stream loads
-			{
-				const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<gptr16>(a));
-				v[k] = make_uint4(t.x, t.y, t.z, t.w);
-			}
-			else
-				v[k] = ld16(a);
+			v[k] = ld16(smin + 16ull * (c < nchunks ? c : nchunks - 1));
 		}
 	};
 	if (stream)
@@ -2648,7 +2387,7 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 		uint32_t full = need < (uint32_t)Chunks ? need : (uint32_t)Chunks;
 		bool more = live && !StreamOnly && (deep || GatherOnly) && full > p.nch;
 		uint32_t from = p.nch;  // the second round gathers chunks [from, full)
-		if (TightR2 && !GatherOnly && __ballot(more))  // wave-uniform: waves without a deep stack skip the extent
+		if (!GatherOnly && __ballot(more))  // wave-uniform: waves without a deep stack skip the extent
 		{
 			// only as far as the fast path reads: the deep stack's header extent, when the first window names it
 			const uint32_t ext = deep_extent(p, et, o);
@@ -2660,7 +2399,7 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 			// the re-gathered window holds only 16-B pieces that lie wholly inside the packet: a piece starting at a
 			// dword could otherwise run past the end of the batch buffer (the packet's tail stays readable from HBM)
 			const uint32_t mis4 = (uint32_t)((uintptr_t)p.g & 3), whole4 = (mis4 + cap) >> 4;
-			const bool realign = Realign && more && past && whole4 >= (uint32_t)Chunks;
+			const bool realign = more && past && whole4 >= (uint32_t)Chunks;
 			if (realign)
 			{
 				p.a0 = (uintptr_t)p.g - mis4;
@@ -2685,11 +2424,9 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	}
 	Fast f{};
 	bool fast = live && !StreamOnly && !GatherOnly && fast_walk(p, cap, prm, f);
-	constexpr bool kL7Regs = (S::R6 & 4) && !StreamOnly && !GatherOnly && !(S::Skip & 8);
-	constexpr bool kWaveHash = (S::R6 & 2) && !StreamOnly && !GatherOnly && !(S::Skip & 1);
-	// R6 bit 2: the fast path's L7 trigger words from the register tables, by the whole wave (converged here)
+	// the fast path's L7 trigger words from the register tables, by the whole wave (converged here), ahead of the hashes
 	L7Pre pre_r{ 0u, 0u, 0u, 0u };
-	if (kL7Regs && __ballot(fast))  // uniform
+	if (__ballot(fast))  // uniform
 		pre_r = l7_pre_regs(p, f, fast && f.payload() && f.l4(), l7_rt, l7_rus);
 
 	// ---- (3) chain walk, hashes, IPv4 checksum: fast path, else the generic walk ----
@@ -2716,14 +2453,9 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	{
 		if (fast)
 		{
-			// the L7 table reads first: their latency hides behind the hashes
-			L7Pre pre = kL7Regs ? pre_r : ((S::Skip & 8) ? L7Pre{ 0u, 0u, 0u, 0u } : fast_l7_pre(p, f));
-			if (!(S::Skip & 1) && !kWaveHash)
-				fast_hashes<(S::Skip & 32) != 0, (S::R6 & 8) != 0>(p, f, fast_to_walk(f, ml), h5, h5d, h2);
-			if (S::Skip & 8)  // diagnostic: the round-3 order (table reads after the hashes)
-				pre = fast_l7_pre(p, f);
-			if (!(S::Skip & 2))
-				fast_l7(p, f, cap, pre);
+			const L7Pre pre = pre_r;  // this lane's copy (keeps the compiler's register order: profiles/r07_retire_switches.txt)
+			fast_hashes(p, f, fast_to_walk(f, ml), h5, h5d, h2);
+			fast_l7(p, f, cap, pre);
 			// a classified HTTP / SSL / DNS payload or a UDP tunnel (VXLAN, GTPv1: an unclassified L7 flag): the
 			// generic walk builds their layers
 			const uint32_t l7 = f.l7();
@@ -2738,12 +2470,11 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 				w.flags |= PCPPX_F_IP_CSUM | (ipc == ips ? PCPPX_F_IP_CSUM_OK : 0);
 			}
 		}
-		else if (!SkipGeneric)
+		else
 		{
 			uint2* lay_out = stage_layers ? reinterpret_cast<uint2*>(prm.layers) + (size_t)i * ml : nullptr;
 			w = walk_chain<Csum ? 2 : 4>(p, cap, prm, lay_out);
-			if (!kWaveHash)
-				hashes<(S::R6 & 8) != 0>(p, w, h5, h5d, h2);
+			hashes(p, w, h5, h5d, h2);
 			if (want_csum && w.v4 >= 0)
 			{
 				ipc = ipv4_checksum(p, w, &ips);
@@ -2815,12 +2546,12 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 			for (uint32_t wi = 0; wi < nwin; wi += 2)
 			{
 				process(va, wi);
-				// R6 bit 4: no loads past the span's last window (a tile of small packets streams 2-3 windows: the padded
-				// loads of windows nwin, nwin + 1 were never consumed, yet held the wave until they returned)
-				if (!(S::R6 & 16) || wi + 2 < nwin)
+				// no loads past the span's last window (a tile of small packets streams 2-3 windows: padded loads of
+				// windows nwin, nwin + 1 would never be consumed, yet hold the wave until they return)
+				if (wi + 2 < nwin)
 					load(va, wi + 2);
 				process(vb, wi + 1);
-				if (!(S::R6 & 16) || wi + 3 < nwin)
+				if (wi + 3 < nwin)
 					load(vb, wi + 3);
 			}
 			if (full)
@@ -2843,19 +2574,8 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 		}
 	}
 
-	// R6 bit 1: the hashes of the whole wave, after the span stream (its two register windows are dead here), from inputs
-	// read out of the LDS window (intact until the layer rows below) or, past it, from HBM
-	HashIn hin = hash_in_none();
-	if (kWaveHash)
-	{
-		if (live && fast)
-			hin = hash_in_fast(p, f, w);
-		else if (live && !SkipGeneric)
-			hin = hash_in_walk(p, w);
-		wave_tuple_hashes(hin, m_nch, h5, h5d, h2);
-	}
-
-	if (in && NT && prm.summary != nullptr)
+	// the records: non-temporal stores (write-once data)
+	if (in && prm.summary != nullptr)
 	{
 		const uint32_t l4b = w.l4i >= 0 ? (uint32_t)w.l4i : 0xFFu;
 		u32x4 s0, s1;
@@ -2865,8 +2585,6 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 		__builtin_nontemporal_store(s0, so);
 		__builtin_nontemporal_store(s1, so + 1);
 	}
-	else if (in && prm.summary != nullptr)
-		write_summary(prm.summary + i, h5, h5d, h2, w.flags, w.n_layers, w.l4i, w.mask, ipc, ips, l4c, l4s);
 	// the 16-B brief: the summary's first half (hashes, flags, chain length, port layer) -- one coalesced 16-B store per
 	// lane; a caller that reads the layer rows derives isPacketOfType from them and the checksum verdicts are the flags
 	if (in && prm.brief != nullptr)
@@ -2879,16 +2597,11 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	if (in && prm.flow_keys != nullptr)
 		__builtin_nontemporal_store(h5, prm.flow_keys + i);
 	if (in && prm.tuples != nullptr)  // the LDS window is still intact here (the rows below reuse it)
-	{
-		if (kWaveHash)
-			write_tuple_in(hin, w, h5, prm.tuples + i);
-		else
-			write_tuple(p, w, h5, prm.tuples + i);
-	}
+		write_tuple(p, w, h5, prm.tuples + i);
 	if (prm.wave_stats != nullptr)  // uniform
 		wave_proto_stats(in, w.mask, w.flags, prm.wave_stats + blockIdx.x);
 	// ---- (5) layer records of fast-path packets: rows built in LDS, written with coalesced stores (whole rows,
-	// zero past the chain, with FillTails; the generic walk writes only the chain's records) ----
+	// zero past the chain: full-line stores; the generic walk writes only the chain's records) ----
 	typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 	typedef __attribute__((address_space(3))) u32x2* lptr64w;
 	// PCPPX_LAYOUT_PACKED: the tile's chains dense in LDS (entry excl + k of the lane's exclusive prefix), stored as one
@@ -2902,7 +2615,7 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 		u32x2* dst = reinterpret_cast<u32x2*>(prm.layers) + (size_t)blockIdx.x * kTile * ml;
 		__syncthreads();  // every lane is done with the header stage
 		lptr64w rows = (lptr64w)(stage);
-		if (fast && !(S::Skip & 4))
+		if (fast)
 			fast_emit(f, cap, ml, [&](uint32_t k, uint2 r) {
 				u32x2 e;
 				e.x = r.x;
@@ -2913,8 +2626,8 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 			for (uint32_t k = 0; k < cnt; ++k)  // the generic walk wrote this lane's chain at its fixed-layout slot
 				rows[excl + k] = dst[lane * ml + k];
 		__syncthreads();
-		// (diagnostic Skip bit 6: only the first half of the run is stored -- the time's sensitivity to the row bytes)
-		const uint32_t stored = (S::Skip & 64) ? total / 2 : total;
+		// (diagnostic HalfPacked: only the first half of the run is stored -- the time's sensitivity to the row bytes)
+		const uint32_t stored = HalfPacked ? total / 2 : total;
 		for (uint32_t r = lane; r < stored; r += kTile)
 			__builtin_nontemporal_store(rows[r], &dst[r]);
 	}
@@ -2929,10 +2642,10 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 	else if (stage_layers)  // uniform
 	{
 		__syncthreads();  // every lane is done with the header stage
-		m_nch[lane] = (fast || GatherOnly) ? (FillTails ? ml : w.n_layers) : 0u;  // records of the row to store
+		m_nch[lane] = (fast || GatherOnly) ? ml : 0u;  // records of the row to store
 		lptr64w rows = (lptr64w)(stage);
 		const uint32_t rs = ml + 1;  // padded row stride (records): breaks the power-of-two bank pattern
-		if (FillTails && (fast || GatherOnly))
+		if (fast || GatherOnly)
 			for (uint32_t k = 0; k < ml; ++k)
 				rows[lane * rs + k] = u32x2{ 0u, 0u };
 		if (fast)
@@ -2952,12 +2665,7 @@ __global__ __launch_bounds__(kTile, MinWaves) void parse_tile_kernel(Params prm)
 		{
 			const uint32_t r = r0 + rr;
 			if (rr < per && r < nrows && kk < m_nch[r])
-			{
-				if (NT)
-					__builtin_nontemporal_store(rows[r * rs + kk], &dst[r * ml + kk]);
-				else
-					dst[r * ml + kk] = rows[r * rs + kk];
-			}
+				__builtin_nontemporal_store(rows[r * rs + kk], &dst[r * ml + kk]);
 		}
 	}
 
@@ -3099,22 +2807,22 @@ __global__ __launch_bounds__(kBlock) void proto_stats_reduce_kernel(const uint4*
 }
 
 // ---- per-flow counters keyed by hash5Tuple (FilterTraffic's flow table, AppWorkerThread.h:99-125) ----
-// A block aggregates 1024 packets at a time in an LDS hash table (LDS atomics), then adds one
-// {packets, bytes} pair per distinct flow to the HBM table: Zipf-skewed traffic puts a hot flow in most
+// A block aggregates one batch of packets at a time in an LDS hash table (LDS atomics), then hands one
+// {packets, bytes} pair per distinct flow on towards the HBM table: Zipf-skewed traffic puts a hot flow in most
 // packets of a batch, and per-packet global atomics on its slot would serialise.
 // Shape variants (block threads, LDS slots, packets per batch) are A/B'd in profiles/r01_ab_flow_shape.txt;
 // every shape keeps fewer packets per batch than LDS slots (hot flows kept only while kept + batch fit).
 constexpr uint32_t kFlowHot = 2;                    // flows with more packets stay in LDS between flushes
 constexpr uint32_t log2u(uint32_t v) { return v <= 1 ? 0 : 1 + log2u(v >> 1); }
 
-// With `packed` (a zeroed u64 per slot, launches of < 2^24 packets) a flush adds {packets, bytes} as one
-// 64-bit atomic (packets << 40 | bytes: < 2^24 packets x < 2^16 B fit 40 bits) and flow_unpack_kernel
-// moves the sums into the table's own counters afterwards: one global atomic per distinct flow and flush.
-// Partitioned flush (kPart): the table is split into P = 2^log2p regions by the key's top hash bits, and instead of
+// A flow's counts travel as one 64-bit word, packets << 40 | bytes (launches of < 2^24 packets x < 2^16 B fit 40 bits).
+// The flush is partitioned: the table is split into P = 2^log2p regions by the key's top hash bits, and instead of
 // global atomics on the table a block appends each distinct key of a batch, {key, packed count}, to its partition's
 // record queue (one global atomic per partition per batch reserves the space); flow_merge_kernel then gives every
 // partition to one block, which folds its queue in LDS and updates its own table region with plain loads and stores.
 // A full queue falls back to atomics on the region.
+// (The unpartitioned flush and the two-pass partitioned flush: git history, profiles/r04g_ab_flow_list.txt and
+// profiles/r04r_ab_flow_onepass.txt.)
 constexpr uint32_t kFlowMaxParts = 1024;  // flow-table partitions (merge blocks) at most
 struct FlowPart
 {
@@ -3154,35 +2862,35 @@ __device__ bool flow_region_add_atomic(uint32_t* keys, unsigned long long* packe
 }
 
 // kDense: keys come from the dense column `dkeys` (pcppx_records.flow_keys) instead of the summaries' hash5.
-// kOnePass (partitioned flush): the hot-flow decision is taken in the partition pass (a hot slot is kept while the kept
-// count stays within the bound, first come first kept) instead of in a pass and a barrier of its own.
-template <uint32_t kFB, uint32_t kFlowLds, uint32_t kFlowBatch, uint32_t kHot = kFlowHot, bool kPrefetch = false,
-          bool kPart = false, bool kDense = false, bool kOnePass = false>
+// kFB / kFlowLds / kFlowBatch / kHot: block threads, LDS slots, packets per batch, hot-flow threshold.
+// The unnamed pointer argument was the unpartitioned flush's accumulator; launches pass nullptr. It stays because
+// dropping it moves the kernel arguments behind it and renumbers the kernel's SGPRs, and the commit that retired the
+// other flush paths was checked by identical machine code (profiles/r07_retire_switches.txt); `capacity` likewise is
+// read by no path any more. Both go with the next change that touches this kernel's code anyway.
+template <uint32_t kFB, uint32_t kFlowLds, uint32_t kFlowBatch, uint32_t kHot, bool kDense>
 __global__ __launch_bounds__(kFB) void flow_count_kernel(const pcppx_summary* __restrict__ sum,
                                                             const uint32_t* __restrict__ caplens, uint32_t n,
                                                             uint32_t* keys, unsigned long long* packets,
                                                             unsigned long long* bytes, uint32_t capacity,
-                                                            unsigned long long* stats, unsigned long long* packed,
-                                                            FlowPart fpart = FlowPart{}, const uint32_t* dkeys = nullptr)
+                                                            unsigned long long* stats, unsigned long long* /* unused */,
+                                                            FlowPart fpart, const uint32_t* dkeys)
 {
-	__shared__ uint32_t s_bin[kPart ? kFlowMaxParts : 1], s_base[kPart ? kFlowMaxParts : 1];  // per-partition counts / offsets
+	__shared__ uint32_t s_bin[kFlowMaxParts], s_base[kFlowMaxParts];  // per-partition counts / offsets
 	__shared__ uint32_t s_key[kFlowLds];
 	__shared__ unsigned long long s_cnt[kFlowLds];  // packets << 40 | bytes (launches hold < 2^24 packets)
 	__shared__ uint32_t s_kept;
 	const uint32_t t = threadIdx.x;
-	const uint32_t m = capacity - 1;
 	unsigned long long z_pk = 0, z_by = 0, lost = 0;  // flow key 0 (PacketUtils.cpp:141-148); table full
 	for (uint32_t j = t; j < kFlowLds; j += kFB)
 	{
 		s_key[j] = 0;
 		s_cnt[j] = 0;
 	}
-	if (kPart)
-		for (uint32_t j = t; j < kFlowMaxParts; j += kFB)
-			s_bin[j] = 0;
+	for (uint32_t j = t; j < kFlowMaxParts; j += kFB)
+		s_bin[j] = 0;
 	__syncthreads();
-	// kPrefetch: the next batch's keys and lengths are loaded into registers before this batch's flush,
-	// so their latency overlaps the flush's HBM reads and atomics
+	// the next batch's keys and lengths are loaded into registers before this batch's flush, so their latency
+	// overlaps the flush's queue stores and atomics
 	constexpr uint32_t kR = kFlowBatch / kFB;
 	uint32_t pkey[kR], plen[kR], pvalid = 0;
 	auto fetch = [&](uint64_t b) {
@@ -3196,17 +2904,15 @@ __global__ __launch_bounds__(kFB) void flow_count_kernel(const pcppx_summary* __
 			pvalid |= (i < n ? 1u : 0u) << r;
 		}
 	};
-	if (kPrefetch)
-		fetch((uint64_t)blockIdx.x * kFlowBatch);
+	fetch((uint64_t)blockIdx.x * kFlowBatch);
 	for (uint64_t base = (uint64_t)blockIdx.x * kFlowBatch; base < n; base += (uint64_t)gridDim.x * kFlowBatch)
 	{
 #pragma unroll
 		for (uint32_t r = 0; r < kR; ++r)
 		{
-			const uint64_t i = base + r * kFB + t;
-			const bool valid = kPrefetch ? ((pvalid >> r) & 1u) != 0 : i < n;
-			const uint32_t key = !valid ? 0u : (kPrefetch ? pkey[r] : (kDense ? dkeys[i] : sum[i].hash5));
-			const uint32_t len = !valid ? 0u : (kPrefetch ? plen[r] : caplens[i]);
+			const bool valid = ((pvalid >> r) & 1u) != 0;
+			const uint32_t key = !valid ? 0u : pkey[r];
+			const uint32_t len = !valid ? 0u : plen[r];
 			if (valid && key == 0)  // flow key 0 (PacketUtils.cpp:141-148): counted, not tabled
 			{
 				z_pk += 1;
@@ -3228,115 +2934,38 @@ __global__ __launch_bounds__(kFB) void flow_count_kernel(const pcppx_summary* __
 				slot = (slot + 1) & (kFlowLds - 1);
 			}
 		}
-		if (kPrefetch)
-			fetch(base + (uint64_t)gridDim.x * kFlowBatch);
+		fetch(base + (uint64_t)gridDim.x * kFlowBatch);
 		if (t == 0)
 			s_kept = 0;
 		__syncthreads();
-		// flush: read the HBM slot of every distinct key first (all loads in flight together); present
-		// keys -- every flow after its first batch -- take no-return atomics, new ones a CAS insert.
-		// Hot flows (more than kFlowHot packets so far) stay in LDS until the block's last batch: every
-		// block meets the top Zipf flows in every batch, and same-address atomics serialise. They are
-		// kept only while they fill at most half of the table, so the next batch always fits.
+		// flush, in one pass over the LDS table: every distinct key is ranked within its partition (LDS), one global
+		// atomic per partition reserves the queue space, then the records are stored.
+		// Hot flows (more than kHot packets so far) stay in LDS until the block's last batch: every block meets the top
+		// Zipf flows in every batch, and a kept flow costs no queue record until then. The decision is taken
+		// in the same pass (first come first kept), while at most half the table minus half a batch is kept, so the
+		// next batch always fits.
 		const bool last = base + (uint64_t)gridDim.x * kFlowBatch >= n;  // uniform
 		constexpr uint32_t kPer = kFlowLds / kFB;
-		if constexpr (kPart && kOnePass)
-		{
-			uint32_t fk[kPer], fs[kPer], fseen[kPer];
-#pragma unroll
-			for (uint32_t u = 0; u < kPer; ++u)
-			{
-				const uint32_t j = u * kFB + t;
-				const uint32_t key = s_key[j];
-				// kept only while at most half the table minus half a batch is kept, so the next batch always fits
-				const bool keep = key != 0 && !last && (s_cnt[j] >> 40) > kHot &&
-				                  atomicAdd(&s_kept, 1u) < kFlowLds / 2 - kFlowBatch / 2;
-				fk[u] = keep ? 0u : key;
-				fs[u] = flow_part(fk[u], fpart.log2p);
-				fseen[u] = fk[u] ? atomicAdd(&s_bin[fs[u]], 1u) : 0u;
-			}
-			__syncthreads();
-			for (uint32_t b = t; b < (1u << fpart.log2p); b += kFB)
-			{
-				const uint32_t c = s_bin[b];
-				s_base[b] = c ? atomicAdd(&fpart.fill[b], c) : 0u;
-				s_bin[b] = 0;
-			}
-			__syncthreads();
-#pragma unroll
-			for (uint32_t u = 0; u < kPer; ++u)
-			{
-				const uint32_t j = u * kFB + t;
-				const uint32_t key = fk[u];
-				if (key == 0)
-					continue;
-				const uint32_t pos = s_base[fs[u]] + fseen[u];
-				const unsigned long long c = s_cnt[j];
-				if (pos < fpart.rec_cap)
-					fpart.recs[(size_t)fs[u] * fpart.rec_cap + pos] = make_uint4(key, 0u, (uint32_t)c, (uint32_t)(c >> 32));
-				else if (!flow_region_add_atomic(keys, packets, bytes, fpart, key, c >> 40, c & ((1ull << 40) - 1)))
-					lost += c >> 40;
-				s_key[j] = 0;
-				s_cnt[j] = 0;
-			}
-			__syncthreads();
-			continue;
-		}
-		uint32_t hot = 0;
-#pragma unroll
-		for (uint32_t u = 0; u < kPer; ++u)
-			hot |= ((s_cnt[u * kFB + t] >> 40) > kHot ? 1u : 0u) << u;
-		if (!last && hot)
-			atomicAdd(&s_kept, (uint32_t)__popc(hot));
-		__syncthreads();
-		const bool keep_hot = !last && s_kept <= kFlowLds / 2 - kFlowBatch / 2;  // uniform
 		uint32_t fk[kPer], fs[kPer], fseen[kPer];
-		if constexpr (kPart)
-		{
-			// queue every distinct key: rank within its partition (LDS), one reservation per partition (global)
-#pragma unroll
-			for (uint32_t u = 0; u < kPer; ++u)
-			{
-				const uint32_t j = u * kFB + t;
-				fk[u] = (keep_hot && ((hot >> u) & 1u)) ? 0u : s_key[j];
-				fs[u] = flow_part(fk[u], fpart.log2p);
-				fseen[u] = fk[u] ? atomicAdd(&s_bin[fs[u]], 1u) : 0u;
-			}
-			__syncthreads();
-			for (uint32_t b = t; b < (1u << fpart.log2p); b += kFB)
-			{
-				const uint32_t c = s_bin[b];
-				s_base[b] = c ? atomicAdd(&fpart.fill[b], c) : 0u;
-				s_bin[b] = 0;
-			}
-			__syncthreads();
-#pragma unroll
-			for (uint32_t u = 0; u < kPer; ++u)
-			{
-				const uint32_t j = u * kFB + t;
-				const uint32_t key = fk[u];
-				if (key == 0)
-					continue;
-				const uint32_t pos = s_base[fs[u]] + fseen[u];
-				const unsigned long long c = s_cnt[j];
-				if (pos < fpart.rec_cap)
-					fpart.recs[(size_t)fs[u] * fpart.rec_cap + pos] = make_uint4(key, 0u, (uint32_t)c, (uint32_t)(c >> 32));
-				else if (!flow_region_add_atomic(keys, packets, bytes, fpart, key, c >> 40, c & ((1ull << 40) - 1)))
-					lost += c >> 40;
-				s_key[j] = 0;
-				s_cnt[j] = 0;
-			}
-			__syncthreads();
-			continue;
-		}
 #pragma unroll
 		for (uint32_t u = 0; u < kPer; ++u)
 		{
 			const uint32_t j = u * kFB + t;
-			fk[u] = (keep_hot && ((hot >> u) & 1u)) ? 0u : s_key[j];
-			fs[u] = (fk[u] * 0x9E3779B1u) & m;
-			fseen[u] = fk[u] ? keys[fs[u]] : 0u;
+			const uint32_t key = s_key[j];
+			const bool keep = key != 0 && !last && (s_cnt[j] >> 40) > kHot &&
+			                  atomicAdd(&s_kept, 1u) < kFlowLds / 2 - kFlowBatch / 2;
+			fk[u] = keep ? 0u : key;
+			fs[u] = flow_part(fk[u], fpart.log2p);
+			fseen[u] = fk[u] ? atomicAdd(&s_bin[fs[u]], 1u) : 0u;
 		}
+		__syncthreads();
+		for (uint32_t b = t; b < (1u << fpart.log2p); b += kFB)
+		{
+			const uint32_t c = s_bin[b];
+			s_base[b] = c ? atomicAdd(&fpart.fill[b], c) : 0u;
+			s_bin[b] = 0;
+		}
+		__syncthreads();
 #pragma unroll
 		for (uint32_t u = 0; u < kPer; ++u)
 		{
@@ -3344,25 +2973,12 @@ __global__ __launch_bounds__(kFB) void flow_count_kernel(const pcppx_summary* __
 			const uint32_t key = fk[u];
 			if (key == 0)
 				continue;
-			uint32_t slot = fs[u];
-			bool done = fseen[u] == key;  // a slot's key never changes once set: a plain read is enough
-			for (uint32_t probe = 0; !done && probe < capacity; ++probe)
-			{
-				const uint32_t prev = atomicCAS(&keys[slot], 0u, key);
-				if (prev == 0u || prev == key)
-					done = true;
-				else
-					slot = (slot + 1) & m;
-			}
-			if (done && packed)
-				atomicAdd(&packed[slot], s_cnt[j]);
-			else if (done)
-			{
-				atomicAdd(&packets[slot], s_cnt[j] >> 40);
-				atomicAdd(&bytes[slot], s_cnt[j] & ((1ull << 40) - 1));
-			}
-			else
-				lost += s_cnt[j] >> 40;
+			const uint32_t pos = s_base[fs[u]] + fseen[u];
+			const unsigned long long c = s_cnt[j];
+			if (pos < fpart.rec_cap)
+				fpart.recs[(size_t)fs[u] * fpart.rec_cap + pos] = make_uint4(key, 0u, (uint32_t)c, (uint32_t)(c >> 32));
+			else if (!flow_region_add_atomic(keys, packets, bytes, fpart, key, c >> 40, c & ((1ull << 40) - 1)))
+				lost += c >> 40;
 			s_key[j] = 0;
 			s_cnt[j] = 0;
 		}
@@ -3380,21 +2996,6 @@ __global__ __launch_bounds__(kFB) void flow_count_kernel(const pcppx_summary* __
 		}
 		if (lost)
 			atomicAdd(&stats[2], lost);
-	}
-}
-
-__global__ __launch_bounds__(kBlock) void flow_unpack_kernel(unsigned long long* packets, unsigned long long* bytes,
-                                                             unsigned long long* packed, uint32_t capacity)
-{
-	for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < capacity; j += gridDim.x * kBlock)
-	{
-		const unsigned long long v = packed[j];
-		if (v)
-		{
-			packets[j] += v >> 40;
-			bytes[j] += v & ((1ull << 40) - 1);
-			packed[j] = 0;
-		}
 	}
 }
 
@@ -3778,27 +3379,24 @@ constexpr int kParseDeepChunks1 = 6;  // the DEEP checksum instance keeps its me
 // checksum launches with opts.window = PCPPX_WINDOW_DEEP: the parse-only instance's two-round 144-B window (tight second
 // round, dword-aligned re-gather) with the span stream; LDS 10 KiB, 4 waves/SIMD; the second stream window is issued
 // after the parse (EarlyB off: this instance's register budget)
-#define PCPPX_PARSE_DEEP_KERNEL                                                                                        \
-	parse_tile_kernel<4, kParseSWin, kParseOnlyChunks, true, kParseDeepChunks1, ParseShape<true, true, true, true, false>>
+#define PCPPX_PARSE_DEEP_KERNEL parse_tile_kernel<4, kParseSWin, kParseOnlyChunks, true, kParseDeepChunks1, ParseShape<false>>
 // parse-only launches with opts.window = PCPPX_WINDOW_SHORT: one 96-B round, LDS 7 KiB (22 waves/CU, 5 waves/SIMD of
 // registers): config 4 0.464 -> 0.432 ms, config 2 43.2 -> 36.3 us, config 5 0.75 -> 1.61 ms (tools/ab variant 60,
 // profiles/r03_ab_windows_persist.txt)
 #define PCPPX_PARSE_SHORT_KERNEL parse_tile_kernel<1, 64, kParseChunks, false, kParseChunks>
 
-// the flow-table shape: 1024-thread blocks, 8192 LDS slots, 4096-packet batches with the next batch prefetched,
-// 256 persistent blocks (profiles/r01_ab_flow_shape.txt, r01_ab_flow_grid.txt)
-#define PCPPX_FLOW_KERNEL flow_count_kernel<1024, 8192, 4096, kFlowHot, true>
-// the partitioned flush (product): the same aggregation over 6144-packet batches (fewer flushes: count + merge
+// the flow-table shape: 1024-thread blocks, 8192 LDS slots, the next batch prefetched, 256 persistent blocks
+// (profiles/r01_ab_flow_shape.txt, r01_ab_flow_grid.txt); 6144-packet batches (fewer flushes than 4096: count + merge
 // 0.178 -> 0.168 ms on config 4, profiles/r04g_ab_flow_list.txt shape 12) with the one-pass flush (-4.6%,
 // profiles/r04r_ab_flow_onepass.txt), then per-partition queues and one merge block per partition
-#define PCPPX_FLOW_PART_KERNEL flow_count_kernel<1024, 8192, kFlowBatchPk, kFlowHot, true, true, false, true>
-#define PCPPX_FLOW_PART_DENSE_KERNEL flow_count_kernel<1024, 8192, kFlowBatchPk, kFlowHot, true, true, true, true>
+#define PCPPX_FLOW_PART_KERNEL flow_count_kernel<1024, 8192, kFlowBatchPk, kFlowHot, false>
+#define PCPPX_FLOW_PART_DENSE_KERNEL flow_count_kernel<1024, 8192, kFlowBatchPk, kFlowHot, true>
 // merge: 512-thread blocks with a 4096-slot LDS table (48 KiB: 3 blocks per CU) over 512 partitions -- count + merge
 // 0.194 -> 0.181 ms on config 4 against 1024 threads / 8192 slots / 256 partitions (profiles/r03_ab_flow_merge.txt);
 // three rounds of queue records in flight (-1 to -2%, profiles/r04f_ab_flow_merge_batch.txt shape 9)
 #define PCPPX_FLOW_MERGE_KERNEL flow_merge_kernel<kFlowMergeThreads, 4096, 2, 3>
 constexpr uint32_t kFlowThreads = 1024, kFlowBatchPk = 6144, kFlowBlocks = 256;
-constexpr uint32_t kPackedMax = (1u << 24) - 1;  // packets per launch the packed LDS/HBM counters hold
+constexpr uint32_t kPackedMax = (1u << 24) - 1;  // packets per launch the packed counts (packets << 40 | bytes) hold
 constexpr uint32_t kFlowPartLog2 = 9;            // flow-table partitions (merge blocks); at most kFlowMaxParts
 constexpr uint32_t kFlowMinRegionLog2 = 12;      // slots per partition at least (capacity 2^21+ -> 512 partitions)
 constexpr uint32_t kFlowMergeThreads = 512;

@@ -30,8 +30,6 @@ def lib() -> C.CDLL:
         P = C.c_void_p
         l.pcppx_ab_parse_device.argtypes = [C.POINTER(abi.Batch), C.POINTER(abi.Opts), C.POINTER(abi.Records), P, C.c_int]
         l.pcppx_ab_parse_device.restype = C.c_int
-        l.pcppx_ab_flow_count_device.argtypes = [P, P, C.c_uint32, P, P, P, C.c_uint32, P, P, P, C.c_int, C.c_uint32]
-        l.pcppx_ab_flow_count_device.restype = C.c_int
         l.pcppx_ab_flow_part.argtypes = [P, P, C.c_uint32, P, P, P, C.c_uint32, P, P, C.c_uint32, P, P, C.c_int]
         l.pcppx_ab_flow_part.restype = C.c_int
         _lib = l
@@ -82,11 +80,3 @@ def parse_on_device(batch, opts: abi.Opts, variant: int, device: str = "cuda:0")
                  torch.cuda.current_stream(device).cuda_stream, variant)
     torch.cuda.synchronize(device)
     return records_from_device(summary, layers, n, opts.max_layers)
-
-
-def flow_count_device(summary, caplens, n: int, keys, packets, bytes_, capacity: int, stats, packed, stream: int,
-                      shape: int, grid: int = 0) -> None:
-    abi.check(lib().pcppx_ab_flow_count_device(abi.ptr(summary), abi.ptr(caplens), n, abi.ptr(keys), abi.ptr(packets),
-                                               abi.ptr(bytes_), capacity, abi.ptr(stats),
-                                               abi.ptr(packed) if packed is not None else None,
-                                               C.c_void_p(stream or 0), shape, grid), "pcppx_ab_flow_count_device")

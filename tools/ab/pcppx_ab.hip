@@ -7,7 +7,7 @@
 //   - tile-kernel shape variants (occupancy, stream windows, cached vs non-temporal loads) and the
 //     stream-only diagnostic, whose measurements chose the product shape (profiles/r01_ab_*.txt);
 //   - read-ceiling diagnostics (tile-shaped and grid-stride streaming reads of the batch bytes);
-//   - the flow-table shape variants (block threads / LDS slots / batch / hot-flow threshold / prefetch).
+//   - the flow-table shape variants (block threads / LDS slots / batch / hot-flow threshold) and merge variants.
 // Entry points are plain C; everything else is hidden.
 #include "../../pcapplusplus_amd/csrc/pcppx_kernels.hip"
 
@@ -19,6 +19,17 @@ namespace
 {
 constexpr int kSlotDw = 33;      // 32 dwords of staged bytes + 1 pad dword: consecutive lanes land on different banks
 constexpr int kStageChunks = 8;  // 8 x 16 B = 128 B staged per packet
+
+// one pcppx_summary with plain stores (the tile kernel builds the same 32 bytes for its non-temporal stores)
+__device__ __forceinline__ void write_summary(pcppx_summary* out, uint32_t h5, uint32_t h5d, uint32_t h2,
+                                              uint32_t flags, uint32_t n_layers, int32_t l4i, uint64_t mask,
+                                              uint32_t ipc, uint32_t ips, uint32_t l4c, uint32_t l4s)
+{
+	uint4 s0 = make_uint4(h5, h5d, h2, flags | (n_layers << 16) | ((l4i >= 0 ? (uint32_t)l4i : 0xFFu) << 24));
+	uint4 s1 = make_uint4((uint32_t)mask, (uint32_t)(mask >> 32), ipc | (ips << 16), l4c | (l4s << 16));
+	reinterpret_cast<uint4*>(out)[0] = s0;
+	reinterpret_cast<uint4*>(out)[1] = s1;
+}
 
 // ================= lane kernel: one lane streams one whole packet (reference / fallback) =================
 __global__ __launch_bounds__(kBlock) void parse_lane_kernel(Params prm)
@@ -221,11 +232,14 @@ using namespace pcppx;
 /* variant: 1 lane kernel; 2 stream-only diagnostic (no header gather / parse; L4 range = [14, caplen));
  * 3 / 4 tile-shaped / grid-stride read of the batch bytes (results written over summary[]); 7 tile-shaped read + the
  * parse's record stores; 29 gather-only diagnostic; 30 / 31 the checksum / parse-only instance marking fast-path
- * packets (flags bit 0x8000); 44 / 52 skip-generic diagnostics; 70 the DEEP checksum instance with the early second
- * stream window; 80 / 81 / 82 parse-only windows of 144 / 128 / 160 B gathered in one round; 83 a 96 + 32-B two-round
- * parse-only window; anything else: the product kernel. Records equal the product's for 1, 70, 80-83 (30 / 31 up to
- * the mark).
- * The shape variants measured in rounds 1-3 are in git history (profiles/r0*_ab_*.txt hold their results). */
+ * packets (flags bit 0x8000); 70 the DEEP checksum instance with the early second stream window; 80 / 81 / 82
+ * parse-only windows of 144 / 128 / 160 B gathered in one round; 83 a 96 + 32-B two-round parse-only window; 120-125
+ * variant 7 under six store policies; 240 / 241 the two-round 144-B parse-only window with a 128 / 112-B first round
+ * (240 is the product's); 260 the SHORT parse-only instance held to 6 waves per SIMD; 270 / 271 the checksum / two-round
+ * parse-only instance storing half of each PACKED run; 0: the product's own launch; anything else: PCPPX_E_INVAL.
+ * Records equal the product's for 1, 70, 80-83, 240, 241, 260 (30 / 31 up to the mark).
+ * The shape variants measured in rounds 1-3 and the round 4-6 switch combinations (stage skips, round-6 bits) are in git
+ * history (profiles/r0*_ab_*.txt, r06*_ab6_*.txt hold their results). */
 PCPPX_AB_API int pcppx_ab_parse_device(const pcppx_batch* b, const pcppx_opts* o, pcppx_records* r, void* hip_stream,
                                        int variant)
 {
@@ -289,12 +303,11 @@ PCPPX_AB_API int pcppx_ab_parse_device(const pcppx_batch* b, const pcppx_opts* o
 		if (variant == 125) hipLaunchKernelGGL(diag_tile_rw_policy<5>, g, t, 0, stream, b->data, b->data_len, per_wave, wo, w_per_wave, so);
 		break;
 	}
-	// diagnostics over the product shapes (ParseShape<NT, FillTails, TightR2, Realign, EarlyB, StreamOnly, MarkFast,
-	// GatherOnly, SkipGeneric>): stream only, gather only, fast-path marks, skip the generic walk
-	case 2: hipLaunchKernelGGL((parse_tile_kernel<5, 128, 6, true, 6, ParseShape<true, true, true, true, true, true>>), grid, dim3(kTile), 0, stream, prm); break;
-	case 29: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 6, ParseShape<true, true, true, true, true, false, false, true>>), grid, dim3(kTile), 0, stream, prm); break;
-	case 30: hipLaunchKernelGGL((parse_tile_kernel<5, 128, 6, true, 6, ParseShape<true, true, true, true, true, false, true>>), grid, dim3(kTile), 0, stream, prm); break;
-	case 31: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 6, ParseShape<true, true, true, true, true, false, true>>), grid, dim3(kTile), 0, stream, prm); break;
+	// diagnostics over the product shapes (ParseShape<EarlyB, ParseDiag>): stream only, gather only, fast-path marks
+	case 2: hipLaunchKernelGGL((parse_tile_kernel<5, 128, 6, true, 6, ParseShape<true, ParseDiag::StreamOnly>>), grid, dim3(kTile), 0, stream, prm); break;
+	case 29: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 6, ParseShape<true, ParseDiag::GatherOnly>>), grid, dim3(kTile), 0, stream, prm); break;
+	case 30: hipLaunchKernelGGL((parse_tile_kernel<5, 128, 6, true, 6, ParseShape<true, ParseDiag::MarkFast>>), grid, dim3(kTile), 0, stream, prm); break;
+	case 31: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 6, ParseShape<true, ParseDiag::MarkFast>>), grid, dim3(kTile), 0, stream, prm); break;
 	// the PCPPX_WINDOW_DEEP checksum instance with the early second stream window (the product's runs it late)
 	case 70: hipLaunchKernelGGL((parse_tile_kernel<4, 128, 9, true, 6>), grid, dim3(kTile), 0, stream, prm); break;
 	// parse-only windows gathered in ONE round for every packet (no dependent second round): 144 B, 128 B, 160 B
@@ -311,27 +324,8 @@ PCPPX_AB_API int pcppx_ab_parse_device(const pcppx_batch* b, const pcppx_opts* o
 	case 241: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 7>), grid, dim3(kTile), 0, stream, prm); break;
 	// round 6: the write-volume sensitivity -- the product instances storing only the first half of each PACKED run
 	// (records wrong past it): 270 the checksum instance, 271 the two-round parse-only instance
-	case 270: hipLaunchKernelGGL((parse_tile_kernel<5, 128, 6, true, 6, ParseShape<true, true, true, true, true, false, false, false, false, 64>>), grid, dim3(kTile), 0, stream, prm); break;
-	case 271: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 8, ParseShape<true, true, true, true, true, false, false, false, false, 64>>), grid, dim3(kTile), 0, stream, prm); break;
-	// round 6: the instances under combinations of the ParseShape R6 switches (bit 0 DPP span reductions, bit 1
-	// wave-wide hashes, bit 2 L7 register tables, bit 3 IPv4-wave hash skip): 200 + R6 for R6 = 0, 1, 2 (the rejected
-	// bits alone), 209: R6 = 12 (bits 2 + 3), 450: R6 = 28 (the product; other combinations measured in r06a-c are in git
-	// history)
-	// the checksum instance (450: R6 = 28), 210 + the two-round parse-only instance, 220 + the SHORT parse-only instance, 230 + the DEEP
-	// checksum instance (its ParseShape with EarlyB, tools/ab variant 70's)
-#define PCPPX_AB_SHAPE(r) ParseShape<true, true, true, true, true, false, false, false, false, 0, r>
-#define PCPPX_AB_R6(base, W, SW, C, CS, C1)                                                                                \
-	case base + 0: hipLaunchKernelGGL((parse_tile_kernel<W, SW, C, CS, C1, PCPPX_AB_SHAPE(0)>), grid, dim3(kTile), 0, stream, prm); break; \
-	case base + 1: hipLaunchKernelGGL((parse_tile_kernel<W, SW, C, CS, C1, PCPPX_AB_SHAPE(1)>), grid, dim3(kTile), 0, stream, prm); break; \
-	case base + 2: hipLaunchKernelGGL((parse_tile_kernel<W, SW, C, CS, C1, PCPPX_AB_SHAPE(2)>), grid, dim3(kTile), 0, stream, prm); break; \
-	case base + 9: hipLaunchKernelGGL((parse_tile_kernel<W, SW, C, CS, C1, PCPPX_AB_SHAPE(12)>), grid, dim3(kTile), 0, stream, prm); break; \
-	case base + 250: hipLaunchKernelGGL((parse_tile_kernel<W, SW, C, CS, C1, PCPPX_AB_SHAPE(28)>), grid, dim3(kTile), 0, stream, prm); break;
-	PCPPX_AB_R6(200, 5, 128, 6, true, 6)
-	PCPPX_AB_R6(210, 1, 64, 9, false, 6)
-	PCPPX_AB_R6(220, 1, 64, 6, false, 6)
-	PCPPX_AB_R6(230, 4, 128, 9, true, 6)
-#undef PCPPX_AB_SHAPE
-#undef PCPPX_AB_R6
+	case 270: hipLaunchKernelGGL((parse_tile_kernel<5, 128, 6, true, 6, ParseShape<true, ParseDiag::HalfPacked>>), grid, dim3(kTile), 0, stream, prm); break;
+	case 271: hipLaunchKernelGGL((parse_tile_kernel<1, 64, 9, false, 8, ParseShape<true, ParseDiag::HalfPacked>>), grid, dim3(kTile), 0, stream, prm); break;
 	case 0: return launch_parse(b, o, r, stream);
 	default: return PCPPX_E_INVAL;  // a variant this build does not hold (older ones: git history)
 	}
@@ -339,9 +333,11 @@ PCPPX_AB_API int pcppx_ab_parse_device(const pcppx_batch* b, const pcppx_opts* o
 }
 
 /* The partitioned flow table over a dense key column with count-kernel shape `shape` (0: the product's
- * 1024 threads / 8192 LDS slots / 4096-packet batches / 256 blocks; 1: 512 / 4096 / 2048 / 768; 2: 256 / 2048 / 1024 /
- * 1536; 3: 1024 / 8192 / 6144 / 512; 12: the round-3 product, 4096-packet batches and a one-round-ahead merge), then the
- * product's merge (shapes 4-11: merge variants; 9: one round ahead). queues / fill: scratch as pcppx_capi.cpp sizes it. */
+ * 1024 threads / 8192 LDS slots / 6144-packet batches / 256 blocks; 1: 512 / 4096 / 2048 / 768; 2: 256 / 2048 / 1024 /
+ * 1536; 3: 1024 / 8192 / 6144 / 512; 12: the round-3 batch of 4096 packets and a one-round-ahead merge; 14 / 15: flows
+ * hot above 4 / 1 packets), then the product's merge (shapes 4-11, 17-19: merge variants; 9: one round ahead). Every
+ * shape flushes in one pass (the two-pass and the unpartitioned flush, shapes 13 and 20: git history,
+ * profiles/r04r_ab_flow_onepass.txt, r04w_ab_flow_unpartitioned.txt). queues / fill: scratch as pcppx_capi.cpp sizes it. */
 PCPPX_AB_API int pcppx_ab_flow_part(const uint32_t* dkeys, const uint32_t* caplens, uint32_t n, uint32_t* keys,
                                     uint64_t* packets, uint64_t* bytes, uint32_t capacity, uint64_t* stats, void* queues,
                                     uint32_t rec_cap, uint32_t* fill, void* hip_stream, int shape)
@@ -359,29 +355,14 @@ PCPPX_AB_API int pcppx_ab_flow_part(const uint32_t* dkeys, const uint32_t* caple
 		hipLaunchKernelGGL(kern, dim3(batches < blocks ? batches : blocks), dim3(threads), 0, stream, nullptr, caplens, n,
 		                   keys, pk, by, capacity, st, nullptr, fp, dkeys);
 	};
-	if (shape == 20)  // no partitions: each batch's distinct keys go straight to the table (packed 64-bit atomics into
-	{                 // `queues` taken as a zeroed u64[capacity] accumulator), then one unpack pass over the table
-		const uint32_t batches = (n + kFlowBatchPk - 1) / kFlowBatchPk;
-		auto* acc = static_cast<unsigned long long*>(queues);
-		hipLaunchKernelGGL((flow_count_kernel<1024, 8192, kFlowBatchPk, kFlowHot, true, false, true>),
-		                   dim3(batches < kFlowBlocks ? batches : kFlowBlocks), dim3(1024), 0, stream, nullptr, caplens, n, keys,
-		                   pk, by, capacity, st, acc, FlowPart{}, dkeys);
-		int rc = check_launch("pcppx_ab_flow_part(unpartitioned)", stream);
-		if (rc != PCPPX_OK)
-			return rc;
-		const uint32_t ub = (capacity + kBlock - 1) / kBlock;
-		hipLaunchKernelGGL(flow_unpack_kernel, dim3(ub < 2048 ? ub : 2048), dim3(kBlock), 0, stream, pk, by, acc, capacity);
-		return check_launch("flow_unpack_kernel", stream);
-	}
 	switch (shape)
 	{
-	case 1: go(flow_count_kernel<512, 4096, 2048, kFlowHot, true, true, true>, 512, 2048, 768); break;
-	case 2: go(flow_count_kernel<256, 2048, 1024, kFlowHot, true, true, true>, 256, 1024, 1536); break;
+	case 1: go(flow_count_kernel<512, 4096, 2048, kFlowHot, true>, 512, 2048, 768); break;
+	case 2: go(flow_count_kernel<256, 2048, 1024, kFlowHot, true>, 256, 1024, 1536); break;
 	case 3: go(PCPPX_FLOW_PART_DENSE_KERNEL, 1024, kFlowBatchPk, 512); break;
-	case 12: go(flow_count_kernel<1024, 8192, 4096, kFlowHot, true, true, true>, 1024, 4096, 256); break;  // r03 batch
-	case 13: go(flow_count_kernel<1024, 8192, kFlowBatchPk, kFlowHot, true, true, true, false>, 1024, kFlowBatchPk, 256); break;  // two-pass flush (r04 before r04r)
-	case 14: go(flow_count_kernel<1024, 8192, kFlowBatchPk, 4, true, true, true, true>, 1024, kFlowBatchPk, 256); break;  // + hot above 4
-	case 15: go(flow_count_kernel<1024, 8192, kFlowBatchPk, 1, true, true, true, true>, 1024, kFlowBatchPk, 256); break;  // + hot above 1
+	case 12: go(flow_count_kernel<1024, 8192, 4096, kFlowHot, true>, 1024, 4096, 256); break;  // r03 batch
+	case 14: go(flow_count_kernel<1024, 8192, kFlowBatchPk, 4, true>, 1024, kFlowBatchPk, 256); break;  // + hot above 4
+	case 15: go(flow_count_kernel<1024, 8192, kFlowBatchPk, 1, true>, 1024, kFlowBatchPk, 256); break;  // + hot above 1
 	default: go(PCPPX_FLOW_PART_DENSE_KERNEL, 1024, kFlowBatchPk, 256); break;
 	}
 	int rc = check_launch("pcppx_ab_flow_part", stream);
@@ -408,51 +389,4 @@ PCPPX_AB_API int pcppx_ab_flow_part(const uint32_t* dkeys, const uint32_t* caple
 	else
 		hipLaunchKernelGGL(PCPPX_FLOW_MERGE_KERNEL, dim3(1u << lp), dim3(kFlowMergeThreads), 0, stream, fp, keys, pk, by, st);
 	return check_launch("flow_merge_kernel", stream);
-}
-
-/* Flow-table shapes 0-12 of profiles/r01_ab_flow_shape.txt (9 = the product's); grid 0 = the shape's default
- * persistent grid. packed: zeroed u64[capacity] scratch (the product's packed accumulator) or NULL. */
-PCPPX_AB_API int pcppx_ab_flow_count_device(const pcppx_summary* sum, const uint32_t* caplens, uint32_t n,
-                                            uint32_t* keys, uint64_t* packets, uint64_t* bytes, uint32_t capacity,
-                                            uint64_t* stats, uint64_t* packed, void* hip_stream, int shape,
-                                            uint32_t grid)
-{
-	if (sum == nullptr || caplens == nullptr || keys == nullptr || capacity == 0 || (capacity & (capacity - 1)) != 0 ||
-	    n > kPackedMax)
-		return PCPPX_E_INVAL;
-	if (n == 0)
-		return PCPPX_OK;
-	hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-	auto* pk = reinterpret_cast<unsigned long long*>(packets);
-	auto* by = reinterpret_cast<unsigned long long*>(bytes);
-	auto* pc = reinterpret_cast<unsigned long long*>(packed);
-	auto* st = reinterpret_cast<unsigned long long*>(stats);
-	auto go = [&](auto kern, uint32_t threads, uint32_t batch, uint32_t def_grid) {
-		const uint32_t batches = (n + batch - 1) / batch;
-		const uint32_t cap = grid ? grid : def_grid;
-		hipLaunchKernelGGL(kern, dim3(batches < cap ? batches : cap), dim3(threads), 0, stream, sum, caplens, n, keys, pk,
-		                   by, capacity, st, pc, FlowPart{}, nullptr);
-	};
-	switch (shape)
-	{
-	case 0: go(flow_count_kernel<256, 2048, 1024>, 256, 1024, 512); break;  // 512 persistent blocks (r01_ab_flow_grid.txt)
-	case 1: go(flow_count_kernel<512, 4096, 2048>, 512, 2048, 512); break;
-	case 2: go(flow_count_kernel<1024, 8192, 4096>, 1024, 4096, 256); break;
-	case 3: go(flow_count_kernel<256, 4096, 2048>, 256, 2048, 512); break;
-	case 4: go(flow_count_kernel<512, 8192, 4096>, 512, 4096, 256); break;
-	case 5: go(flow_count_kernel<1024, 8192, 2048>, 1024, 2048, 256); break;
-	case 6: go(flow_count_kernel<1024, 8192, 4096, 1>, 1024, 4096, 256); break;
-	case 7: go(flow_count_kernel<1024, 8192, 4096, 4>, 1024, 4096, 256); break;
-	case 8: go(flow_count_kernel<1024, 8192, 4096, 8>, 1024, 4096, 256); break;
-	case 10: go(flow_count_kernel<512, 4096, 2048, kFlowHot, true>, 512, 2048, 512); break;
-	case 11: go(flow_count_kernel<1024, 4096, 2048, kFlowHot, true>, 1024, 2048, 512); break;
-	case 12: go(flow_count_kernel<1024, 8192, 6144, kFlowHot, true>, 1024, 6144, 256); break;
-	default: go(PCPPX_FLOW_KERNEL, kFlowThreads, 4096, kFlowBlocks); break;
-	}
-	int rc = check_launch("pcppx_ab_flow_count_device", stream);
-	if (rc != PCPPX_OK || pc == nullptr)
-		return rc;
-	const uint32_t ub = (capacity + kBlock - 1) / kBlock;
-	hipLaunchKernelGGL(flow_unpack_kernel, dim3(ub < 2048 ? ub : 2048), dim3(kBlock), 0, stream, pk, by, pc, capacity);
-	return check_launch("flow_unpack_kernel", stream);
 }

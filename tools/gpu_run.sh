@@ -18,7 +18,7 @@
 #   ab:<cfg>:<cases>               interleaved A/B of tools/ab_kernels.py cases (comma list) on config <cfg> (3s64: config 3
 #                                  at 64 B), 10M packets, 12 rounds -> <tag>_ab_cfg<cfg>.txt
 #   ab6:<cfg>:<variants>           interleaved A/B of tools/ab_r06.py variants (-1 the round-5 kernel, 0 the product,
-#                                  200+/210+/220+ R6 combinations) on bench.py's launch of <cfg> -> <tag>_ab6_cfg<cfg>.txt
+#                                  others: tools/ab/pcppx_ab.hip) on bench.py's launch of <cfg> -> <tag>_ab6_cfg<cfg>.txt
 #   cmd:<shell command>            anything else, under a 600 s limit
 set -o pipefail
 TAG=$1
