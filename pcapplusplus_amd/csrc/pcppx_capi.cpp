@@ -489,7 +489,10 @@ constexpr uint32_t kMinRun = 4096;  // a shorter run that stops at a discontinui
 // Contiguous runs are not staged: *direct is then the source of the H2D copy, page-locked or not (the runtime DMAs a
 // pageable range as fast as a page-locked one, 56 GB/s from a file map, profiles/r04f_h2d_probe.txt, where a copy
 // into staging first ran at 30 GB/s per thread); scattered packets are gathered into the staging.
-uint32_t stage_chunk(Slot& s, const pcppx_batch* b, uint32_t i, size_t* pos_out, const uint8_t** direct)
+// *pos_out: the bytes to copy to the device; *len_out: the chunk's data_len there, which is larger only when a gathered
+// chunk holds an oversize packet (no byte of it is staged, but its descriptor must stay in bounds).
+uint32_t stage_chunk(Slot& s, const pcppx_batch* b, uint32_t i, size_t* pos_out, uint64_t* len_out,
+                     const uint8_t** direct)
 {
 	*direct = nullptr;
 	{
@@ -509,24 +512,33 @@ uint32_t stage_chunk(Slot& s, const pcppx_batch* b, uint32_t i, size_t* pos_out,
 			}
 			*direct = b->data + base;
 			*pos_out = bytes;
+			*len_out = bytes;
 			return j;
 		}
 	}
 	size_t pos = 0;
+	uint64_t oversize = 0;  // the largest in-bounds caplen above PCPPX_MAX_CAPLEN
 	uint32_t j = i;
 	while (j < b->n && j - i < kChunkPackets)
 	{
 		const uint64_t off = b->offsets[j];
 		const uint32_t cap = b->caplens[j];
 		const bool in_bounds = off + cap <= b->data_len && off + cap >= off;
-		const size_t take = in_bounds ? cap : 0;
+		// the kernels read the bytes of no other packet (desc_flags: PCPPX_F_BAD_DESC, PCPPX_F_OVERSIZE)
+		const bool parsed = in_bounds && cap <= PCPPX_MAX_CAPLEN;
+		const size_t take = parsed ? cap : 0;
 		if (pos + take > kChunkBytes && j > i)
 			break;
-		if (in_bounds && cap <= kChunkBytes)
+		if (parsed)
 		{
 			std::memcpy(s.h_data + pos, b->data + off, cap);
 			s.h_off[j - i] = pos;
 			pos += cap;
+		}
+		else if (in_bounds)
+		{
+			s.h_off[j - i] = 0;  // kernel flags PCPPX_F_OVERSIZE, as the device path does: no bytes staged
+			oversize = cap > oversize ? cap : oversize;
 		}
 		else
 			s.h_off[j - i] = ~0ull >> 1;  // kernel flags PCPPX_F_BAD_DESC
@@ -534,12 +546,15 @@ uint32_t stage_chunk(Slot& s, const pcppx_batch* b, uint32_t i, size_t* pos_out,
 		++j;
 	}
 	*pos_out = pos;
+	*len_out = pos > oversize ? pos : oversize;
 	return j;
 }
 
 bool upload_chunk(Slot& s, size_t pos, uint32_t cnt, const uint8_t* direct = nullptr)
 {
-	return ok(hipMemcpyAsync(s.d_data, direct ? direct : s.h_data, pos ? pos : 1, hipMemcpyHostToDevice, s.st)) &&
+	// a chunk of zero bytes copies one placeholder byte, from the slot's own staging: a direct run of empty packets may
+	// start at the very end of the caller's buffer
+	return ok(hipMemcpyAsync(s.d_data, direct && pos ? direct : s.h_data, pos ? pos : 1, hipMemcpyHostToDevice, s.st)) &&
 	       ok(hipMemcpyAsync(s.d_off, s.h_off, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, s.st)) &&
 	       ok(hipMemcpyAsync(s.d_cap, s.h_cap, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s.st));
 }
@@ -631,12 +646,13 @@ int parse_host_run(pcppx_ctx* c, const pcppx_batch* b, const pcppx_opts* o, pcpp
 			drain(c->copier, s, r, direct_out, dense, dense_direct, &written);
 		}
 		size_t pos = 0;
+		uint64_t len = 0;
 		const uint8_t* direct = nullptr;
-		const uint32_t j = stage_chunk(s, b, i, &pos, &direct);
+		const uint32_t j = stage_chunk(s, b, i, &pos, &len, &direct);
 		const uint32_t cnt = j - i;
 		if (!upload_chunk(s, pos, cnt, direct))
 			return PCPPX_E_HIP;
-		pcppx_batch db{ s.d_data, s.d_off, s.d_cap, pos, cnt, b->linktype, 0 };
+		pcppx_batch db{ s.d_data, s.d_off, s.d_cap, len, cnt, b->linktype, 0 };
 		pcppx_records dr{};
 		dr.summary = r->summary ? s.d_sum : nullptr;
 		dr.brief = r->brief ? s.d_brief : nullptr;
@@ -719,15 +735,16 @@ int filter_host_run(pcppx_ctx* c, const pcppx_batch* b, const pcppx_match_spec* 
 			s.busy = false;
 		}
 		size_t pos = 0;
+		uint64_t len = 0;
 		const uint8_t* direct = nullptr;
-		const uint32_t j = stage_chunk(s, b, i, &pos, &direct);
+		const uint32_t j = stage_chunk(s, b, i, &pos, &len, &direct);
 		const uint32_t cnt = j - i;
 		if (!upload_chunk(s, pos, cnt, direct))
 			return PCPPX_E_HIP;
 		// the flow table is shared by consecutive chunks: chunk k's lookups run after chunk k-1's marks
 		if (prev != nullptr && !ok(hipStreamWaitEvent(s.st, prev->done, 0)))
 			return PCPPX_E_HIP;
-		pcppx_batch db{ s.d_data, s.d_off, s.d_cap, pos, cnt, b->linktype, 0 };
+		pcppx_batch db{ s.d_data, s.d_off, s.d_cap, len, cnt, b->linktype, 0 };
 		pcppx_records dr{};
 		dr.summary = s.d_sum;
 		dr.layers = s.d_lay;

@@ -183,8 +183,9 @@ def test_gpu_sized_batches(engine, size):
 def test_gpu_host_path_matches_device_path(engine):
     """pcppx_parse_batch_host (chunked, three slots) equals the device path: packed pageable input
     (staged by the copy threads), pinned input (DMA straight from the caller's bytes), pinned input and
-    pinned record arrays (records DMA'd straight into them, no drain copy), and a gapped batch (per-packet
-    gather)."""
+    pinned record arrays (records DMA'd straight into them, no drain copy), and a gapped batch (gaps of 0-16 B,
+    below the 256-B threshold: still one direct copy of the run; the per-packet gather is covered by
+    test_host_staging.py)."""
     from pcapplusplus_amd.engine import pinned_copy, pinned_records
 
     b = synth.config(3, 600_000)
