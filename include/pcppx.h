@@ -532,6 +532,87 @@ PCPPX_API int pcppx_steer_device(pcppx_ctx* ctx, const pcppx_batch* batch, const
 /* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
 PCPPX_API int pcppx_steer_reference(const pcppx_batch* batch, const pcppx_steer_spec* spec, pcppx_steering* out);
 
+/* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
+ * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
+ * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in
+ * pcap_offline_filter over a compiled bpf_program with len = caplen (PcapFilter.cpp:122-127). The compiler stays with
+ * the caller (libpcap's pcap_compile); this is the interpreter, as a kernel: one or several validated programs run over
+ * every packet of a batch in HBM, with no parse, and the verdicts come out as the columns select and steer consume:
+ * matched[] is pcppx_select_spec.keep, bucket[] (the first accepting program; 0xFF = none, i.e. >= n_buckets = not
+ * steered) is pcppx_steer_spec.bucket. Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * The machine is libpcap's userland bpf_filter with no auxiliary data, per packet i:
+ *   state    A, X and M[0..15] are 32-bit and start at zero for every program; buflen = caplens[i]; wirelen =
+ *            frame_lens[i], or caplens[i] when frame_lens is NULL (the reference's own call, PcapFilter.cpp:124-125).
+ *   ld abs   LD|W|ABS, LD|H|ABS, LD|B|ABS: A = the big-endian 4 / 2 / 1 bytes at k. The packet is rejected (the program
+ *            returns 0) when k > buflen || size > buflen - k (for B: k >= buflen).
+ *   ld ind   LD|W|IND, LD|H|IND, LD|B|IND: the same at X + k; rejected when k > buflen || X > buflen - k ||
+ *            size > buflen - (X + k): nothing wraps 32 bits.
+ *   ldx msh  LDX|B|MSH: X = (P[k] & 0xf) << 2, bounded as the B load.
+ *   others   LD|IMM (A = k), LD|MEM (A = M[k]), LD|W|LEN (A = wirelen), LDX|W|IMM, LDX|W|MEM, LDX|W|LEN the same
+ *            into X; ST (M[k] = A), STX (M[k] = X).
+ *   alu      ALU|ADD, SUB, MUL, DIV, MOD, AND, OR, XOR, LSH, RSH with K or X as the operand, modulo 2^32; DIV or MOD
+ *            by X == 0 rejects the packet; a shift by 32 or more gives 0. ALU|NEG: A = -A.
+ *   jumps    JMP|JA: pc += k. JMP|JEQ, JGT, JGE, JSET with K or X: pc += (condition ? jt : jf); unsigned comparisons;
+ *            JSET tests A & operand.
+ *   rest     RET|K returns k, RET|A returns A; MISC|TAX (X = A), MISC|TXA (A = X).
+ * A packet of any caplen (0, or above PCPPX_MAX_CAPLEN) is filtered: BPF is not a parse. batch->linktype is ignored
+ * (it mattered when the program was compiled). eBPF, the Linux SKF_AD_* ancillary offsets and auxiliary VLAN data are
+ * out of scope: such offsets are ordinary out-of-range loads and reject, as in pcap_offline_filter.
+ *
+ * Validation (pcppx_bpf_validate; pcppx_bpf_load applies it per program), PCPPX_E_INVAL otherwise:
+ * 1 <= n_insns <= PCPPX_BPF_MAX_INSNS; every opcode is one of those above; a MEM / ST / STX index is below
+ * PCPPX_BPF_MEMWORDS; DIV or MOD by a constant 0 is refused; for JA, i + 1 + k does not wrap and is < n_insns; for the
+ * conditional jumps i + 1 + jt and i + 1 + jf are < n_insns; the last instruction is a RET. Jumps go forward only, so
+ * every program ends within n_insns steps. */
+typedef struct pcppx_bpf_insn { /* layout of struct bpf_insn / sock_filter: a bpf_program's bf_insns can be passed as is */
+	uint16_t code;
+	uint8_t jt, jf;
+	uint32_t k;
+} pcppx_bpf_insn;
+#define PCPPX_BPF_MAX_INSNS 4096   /* per program (BPF_MAXINSNS) */
+#define PCPPX_BPF_MAX_PROGRAMS 16
+#define PCPPX_BPF_MEMWORDS 16
+typedef struct pcppx_bpf_prog { /* host memory */
+	const pcppx_bpf_insn* insns;
+	uint32_t n_insns;
+	uint32_t reserved;
+} pcppx_bpf_prog;
+typedef struct pcppx_bpf pcppx_bpf; /* validated programs resident on a context's GPU */
+
+/* pcppx_bpf_verdicts.totals words */
+#define PCPPX_BPF_MATCHED 0  /* packets some program accepted */
+#define PCPPX_BPF_BAD_DESC 1 /* offsets[i] + caplens[i] > data_len (or wraps 64 bits): never read, rejected */
+#define PCPPX_BPF_TOTALS 8   /* words 2-7 zero */
+typedef struct pcppx_bpf_verdicts { /* device pointers for _device, host for _reference; each column may be NULL */
+	uint8_t* matched; /* n: 1 iff some program returns non-zero, else 0 (select's keep[]) */
+	uint8_t* bucket;  /* n: index of the first program (in load order) that returns non-zero, else 0xFF (steer's column) */
+	uint32_t* ret;    /* n: that program's return value (bpf_filter's result: the snap length), else 0 */
+	uint64_t* totals; /* required: PCPPX_BPF_TOTALS words, overwritten by each call */
+} pcppx_bpf_verdicts;
+
+/* The validation rules above over one program in host memory; PCPPX_OK or PCPPX_E_INVAL. Host only, no GPU. */
+PCPPX_API int pcppx_bpf_validate(const pcppx_bpf_insn* insns, uint32_t n_insns);
+/* Validate n_progs (1..PCPPX_BPF_MAX_PROGRAMS) programs and copy them, back to back in load order, into one buffer on
+ * ctx's GPU. The handle is independent of the caller's arrays afterwards; it may be used by any number of calls. */
+PCPPX_API int pcppx_bpf_load(pcppx_ctx* ctx, const pcppx_bpf_prog* progs, uint32_t n_progs, pcppx_bpf** out);
+PCPPX_API void pcppx_bpf_free(pcppx_bpf* f); /* waits for queued work that uses f */
+/* Run f's programs, in load order, over every packet of a device batch (frame_lens: device, n entries, or NULL); a
+ * packet's verdict is that of the first program that returns non-zero (later programs are not run for it). A packet
+ * with a bad descriptor gets matched 0, bucket 0xFF, ret 0 and counts in PCPPX_BPF_BAD_DESC; its bytes are never read.
+ * Only the first n entries of each non-NULL column are written. Source bytes are read only through aligned 4-byte
+ * words that hold at least one byte of an in-bounds packet. The output is a pure function of the inputs; the totals are
+ * integer counts. PCPPX_E_INVAL before any device work: a null ctx, f, batch, out or totals. n == 0 is legal and
+ * writes zero totals. The work is queued on hip_stream and the call returns without waiting (the totals stay on the
+ * device); calls share no scratch, so calls on different streams may overlap. */
+PCPPX_API int pcppx_bpf_device(pcppx_ctx* ctx, const pcppx_bpf* f, const pcppx_batch* batch, const uint32_t* frame_lens,
+                               pcppx_bpf_verdicts* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. PCPPX_E_INVAL: a
+ * null progs, insns pointer, batch, out or totals; n_progs 0 or above PCPPX_BPF_MAX_PROGRAMS; a non-zero reserved
+ * field; a program that does not validate (pcppx_bpf_load refuses the same). */
+PCPPX_API int pcppx_bpf_reference(const pcppx_bpf_prog* progs, uint32_t n_progs, const pcppx_batch* batch,
+                                  const uint32_t* frame_lens, pcppx_bpf_verdicts* out);
+
 /* ---- host ingest: pcap / pcapng captures into packed batch buffers ---- */
 typedef struct pcppx_pcap pcppx_pcap;
 /* Open a capture; the format comes from its first 4 bytes as IFileReaderDevice::createReader

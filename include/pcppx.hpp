@@ -1931,6 +1931,80 @@ struct MatchSpec
 	}
 };
 
+/* A compiled classic BPF program, in the shape of BpfFilterWrapper (Pcap++/header/PcapFilter.h): the caller compiles
+ * the filter string with its own libpcap (pcap_compile) and hands over bpf_program.bf_insns, whose layout
+ * pcppx_bpf_insn has. matchPacketWithFilter runs it on the host over one packet with len = caplen, as
+ * BpfFilterWrapper::matchPacketWithFilter does (PcapFilter.cpp:122-127); Engine::matchBatch runs it over a device
+ * batch. */
+class BpfFilter
+{
+public:
+	BpfFilter() = default;
+	~BpfFilter() { pcppx_bpf_free(m_Loaded); }
+	BpfFilter(const BpfFilter&) = delete;
+	BpfFilter& operator=(const BpfFilter&) = delete;
+
+	/* false (and no program set) when pcppx_bpf_validate refuses it */
+	bool setProgram(const pcppx_bpf_insn* insns, uint32_t n)
+	{
+		pcppx_bpf_free(m_Loaded);
+		m_Loaded = nullptr;
+		m_Ctx = nullptr;
+		m_Insns.clear();
+		if (pcppx_bpf_validate(insns, n) != PCPPX_OK)
+			return false;
+		m_Insns.assign(insns, insns + n);
+		return true;
+	}
+	bool isSet() const { return !m_Insns.empty(); }
+
+	/* an unset filter matches every packet, as an empty filter string does in the reference */
+	bool matchPacketWithFilter(const RawPacket* rawPacket) const
+	{
+		if (rawPacket == nullptr)
+			return false;
+		return matches(rawPacket->getRawData(), (uint32_t)rawPacket->getRawDataLen());
+	}
+	bool matches(const uint8_t* packetData, uint32_t packetDataLength) const
+	{
+		if (m_Insns.empty())
+			return true;
+		const uint64_t offset = 0;
+		pcppx_batch b{};
+		b.data = packetData;
+		b.offsets = &offset;
+		b.caplens = &packetDataLength;
+		b.data_len = packetDataLength;
+		b.n = 1;
+		const pcppx_bpf_prog prog{ m_Insns.data(), (uint32_t)m_Insns.size(), 0 };
+		uint8_t matched = 0;
+		uint64_t totals[PCPPX_BPF_TOTALS];
+		pcppx_bpf_verdicts v{ &matched, nullptr, nullptr, totals };
+		check(pcppx_bpf_reference(&prog, 1, &b, nullptr, &v), "pcppx_bpf_reference");
+		return matched != 0;
+	}
+
+private:
+	friend class Engine;
+	/* the program resident on ctx's GPU: loaded on first use, again when the program or the engine changes */
+	const pcppx_bpf* loaded(pcppx_ctx* ctx) const
+	{
+		if (m_Loaded == nullptr || m_Ctx != ctx)
+		{
+			pcppx_bpf_free(m_Loaded);
+			m_Loaded = nullptr;
+			const pcppx_bpf_prog prog{ m_Insns.data(), (uint32_t)m_Insns.size(), 0 };
+			check(pcppx_bpf_load(ctx, &prog, 1, &m_Loaded), "pcppx_bpf_load");
+			m_Ctx = ctx;
+		}
+		return m_Loaded;
+	}
+
+	std::vector<pcppx_bpf_insn> m_Insns;
+	mutable pcppx_bpf* m_Loaded = nullptr;
+	mutable pcppx_ctx* m_Ctx = nullptr;
+};
+
 /* One GPU worker for the batch API: a pcppx context. */
 class Engine
 {
@@ -1975,6 +2049,17 @@ public:
 		return st;
 	}
 	void resetFilter(uint32_t flowTableSlots = 0) { check(pcppx_filter_reset(m_Ctx, flowTableSlots), "pcppx_filter_reset"); }
+
+	/* matchPacketWithFilter for every packet of a device batch (pcppx_bpf_device): deviceBatch, frameLens (may be null:
+	 * len = caplen, the reference's own call) and out hold device pointers; out.matched feeds pcppx_select_spec.keep.
+	 * Queued on hipStream; returns without waiting. The filter must have a program set. */
+	void matchBatch(const BpfFilter& filter, const pcppx_batch& deviceBatch, const uint32_t* frameLens,
+	                pcppx_bpf_verdicts& out, void* hipStream = nullptr) const
+	{
+		if (!filter.isSet())
+			throw Error(PCPPX_E_INVAL, "matchBatch: no program set");
+		check(pcppx_bpf_device(m_Ctx, filter.loaded(m_Ctx), &deviceBatch, frameLens, &out, hipStream), "pcppx_bpf_device");
+	}
 
 	pcppx_ctx* handle() const { return m_Ctx; }
 

@@ -219,6 +219,65 @@ def steer_reference(batch: Batch, spec: SteerSpec, out: Steering) -> None:
     check(load_engine().pcppx_steer_reference(C.byref(batch), C.byref(spec), C.byref(out)), "pcppx_steer_reference")
 
 
+# pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
+BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
+BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
+BPF_TOTALS = 8
+BPF_FIELDS = ("matched", "bad_desc")
+BPF_NO_BUCKET = 0xFF
+BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])  # pcppx_bpf_insn
+assert BPF_INSN_DTYPE.itemsize == 8
+
+
+class BpfInsn(C.Structure):
+    """pcppx_bpf_insn: struct bpf_insn / sock_filter."""
+    _fields_ = [("code", C.c_uint16), ("jt", C.c_uint8), ("jf", C.c_uint8), ("k", C.c_uint32)]
+
+
+class BpfProg(C.Structure):
+    """pcppx_bpf_prog: one program in host memory."""
+    _fields_ = [("insns", C.c_void_p), ("n_insns", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BpfVerdicts(C.Structure):
+    """pcppx_bpf_verdicts: the per-packet columns (each may be None) and the totals."""
+    _fields_ = [("matched", C.c_void_p), ("bucket", C.c_void_p), ("ret", C.c_void_p), ("totals", C.c_void_p)]
+
+
+def bpf_program(insns) -> np.ndarray:
+    """A program as a contiguous BPF_INSN_DTYPE array: from such an array, or from (code, jt, jf, k) rows."""
+    if isinstance(insns, np.ndarray) and insns.dtype == BPF_INSN_DTYPE:
+        return np.ascontiguousarray(insns)
+    return np.array([tuple(int(x) for x in row) for row in insns], dtype=BPF_INSN_DTYPE)
+
+
+def make_bpf_progs(programs):
+    """(pcppx_bpf_prog array, the instruction arrays it points to: keep them alive) for a list of programs."""
+    arrays = [bpf_program(p) for p in programs]
+    progs = (BpfProg * max(len(arrays), 1))()
+    for q, a in enumerate(arrays):
+        progs[q] = BpfProg(a.ctypes.data, len(a), 0)
+    return progs, arrays
+
+
+def bpf_validate(insns) -> bool:
+    """pcppx_bpf_validate: whether pcppx_bpf_load would take the program (host only)."""
+    a = bpf_program(insns)
+    return load_engine().pcppx_bpf_validate(a.ctypes.data if len(a) else None, len(a)) == OK
+
+
+def bpf_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(BPF_FIELDS)}
+
+
+def bpf_reference(programs, batch: Batch, frame_lens, out: BpfVerdicts) -> None:
+    """pcppx_bpf_reference: pcppx_bpf_device's contract in plain C++ over host pointers (no GPU). frame_lens: the
+    address of n u32, or None; out's arrays and totals are filled in place."""
+    progs, keep = make_bpf_progs(programs)
+    check(load_engine().pcppx_bpf_reference(progs, len(keep), C.byref(batch), frame_lens, C.byref(out)),
+          "pcppx_bpf_reference")
+
+
 def ipv4_to_int(dotted: str) -> int:
     """IPv4Address::toInt(): the address bytes in memory order read as a little-endian u32."""
     b = bytes(int(x) for x in dotted.split("."))
@@ -366,6 +425,16 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_steer_device.restype = C.c_int
     lib.pcppx_steer_reference.argtypes = [C.POINTER(Batch), C.POINTER(SteerSpec), C.POINTER(Steering)]
     lib.pcppx_steer_reference.restype = C.c_int
+    lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
+    lib.pcppx_bpf_validate.restype = C.c_int
+    lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
+    lib.pcppx_bpf_load.restype = C.c_int
+    lib.pcppx_bpf_free.argtypes = [P]
+    lib.pcppx_bpf_free.restype = None
+    lib.pcppx_bpf_device.argtypes = [P, P, C.POINTER(Batch), P, C.POINTER(BpfVerdicts), P]
+    lib.pcppx_bpf_device.restype = C.c_int
+    lib.pcppx_bpf_reference.argtypes = [P, C.c_uint32, C.POINTER(Batch), P, C.POINTER(BpfVerdicts)]
+    lib.pcppx_bpf_reference.restype = C.c_int
     for name in ("pcppx_device_count", "pcppx_open", "pcppx_sync", "pcppx_parse_batch_device",
                  "pcppx_parse_batch_host", "pcppx_flow_count_device"):
         getattr(lib, name).restype = C.c_int
@@ -382,6 +451,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_pcap_read_batch", "pcppx_pcap_read_batch_ex", "pcppx_pcap_map_batch", "pcppx_pcap_close", "pcppx_host_alloc", "pcppx_host_free",
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
+    "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 
 

@@ -1449,3 +1449,347 @@ extern "C"
 		return PCPPX_OK;
 	}
 }
+
+// ---- bpf: classic BPF programs over the packets of a batch (include/pcppx.h, bpf) ----
+struct pcppx_bpf
+{
+	int device = 0;
+	pcppx_bpf_insn* d_insns = nullptr;
+	pcppx::BpfPrograms progs{};
+	// recorded after every pcppx_bpf_device launch (on whatever stream): pcppx_bpf_free waits for it
+	hipEvent_t used = nullptr;
+	bool pending = false;
+};
+
+namespace
+{
+// the opcodes of the machine in include/pcppx.h (the BPF_* values of <pcap/bpf.h>)
+enum : uint16_t
+{
+	kBpfLdW = 0x00, kBpfLdH = 0x08, kBpfLdB = 0x10,
+	kBpfImm = 0x00, kBpfAbs = 0x20, kBpfInd = 0x40, kBpfMem = 0x60, kBpfLen = 0x80, kBpfMsh = 0xa0,
+	kBpfLd = 0x00, kBpfLdx = 0x01, kBpfSt = 0x02, kBpfStx = 0x03, kBpfAlu = 0x04, kBpfJmp = 0x05, kBpfRet = 0x06,
+	kBpfMisc = 0x07,
+	kBpfK = 0x00, kBpfX = 0x08, kBpfA = 0x10,
+	kBpfAdd = 0x00, kBpfSub = 0x10, kBpfMul = 0x20, kBpfDiv = 0x30, kBpfOr = 0x40, kBpfAnd = 0x50, kBpfLsh = 0x60,
+	kBpfRsh = 0x70, kBpfNeg = 0x80, kBpfMod = 0x90, kBpfXor = 0xa0,
+	kBpfJa = 0x00, kBpfJeq = 0x10, kBpfJgt = 0x20, kBpfJge = 0x30, kBpfJset = 0x40,
+	kBpfTax = 0x00, kBpfTxa = 0x80,
+};
+
+bool bpf_is_ret(uint16_t code)
+{
+	return code == (kBpfRet | kBpfK) || code == (kBpfRet | kBpfA);
+}
+
+// one instruction at position i of n: a known opcode with legal operands
+bool bpf_insn_ok(const pcppx_bpf_insn& in, uint32_t i, uint32_t n)
+{
+	const uint16_t c = in.code;
+	switch (c)
+	{
+	case kBpfLd | kBpfLdW | kBpfAbs:
+	case kBpfLd | kBpfLdH | kBpfAbs:
+	case kBpfLd | kBpfLdB | kBpfAbs:
+	case kBpfLd | kBpfLdW | kBpfInd:
+	case kBpfLd | kBpfLdH | kBpfInd:
+	case kBpfLd | kBpfLdB | kBpfInd:
+	case kBpfLdx | kBpfLdB | kBpfMsh:
+	case kBpfLd | kBpfImm:
+	case kBpfLdx | kBpfImm:
+	case kBpfLd | kBpfLdW | kBpfLen:
+	case kBpfLdx | kBpfLdW | kBpfLen:
+	case kBpfMisc | kBpfTax:
+	case kBpfMisc | kBpfTxa:
+	case kBpfAlu | kBpfNeg:
+		return true;
+	case kBpfLd | kBpfMem:
+	case kBpfLdx | kBpfMem:
+	case kBpfSt:
+	case kBpfStx:
+		return in.k < PCPPX_BPF_MEMWORDS;
+	case kBpfJmp | kBpfJa:
+		return in.k < n && (uint64_t)i + 1 + in.k < n;
+	default:
+		break;
+	}
+	if (bpf_is_ret(c))
+		return true;
+	const uint16_t cls = c & 0x07, src = c & 0x08, op = c & 0xf0;
+	if ((c & ~0xffu) != 0)
+		return false;
+	if (cls == kBpfAlu)
+	{
+		switch (op)
+		{
+		case kBpfAdd:
+		case kBpfSub:
+		case kBpfMul:
+		case kBpfOr:
+		case kBpfAnd:
+		case kBpfXor:
+		case kBpfLsh:
+		case kBpfRsh:
+			return true;
+		case kBpfDiv:
+		case kBpfMod:
+			return src == kBpfX || in.k != 0;
+		default:
+			return false;
+		}
+	}
+	if (cls == kBpfJmp && (op == kBpfJeq || op == kBpfJgt || op == kBpfJge || op == kBpfJset))
+		return (uint64_t)i + 1 + in.jt < n && (uint64_t)i + 1 + in.jf < n;
+	return false;
+}
+
+int bpf_validate(const pcppx_bpf_insn* insns, uint32_t n)
+{
+	if (insns == nullptr || n < 1 || n > PCPPX_BPF_MAX_INSNS)
+		return PCPPX_E_INVAL;
+	for (uint32_t i = 0; i < n; ++i)
+		if (!bpf_insn_ok(insns[i], i, n))
+			return PCPPX_E_INVAL;
+	return bpf_is_ret(insns[n - 1].code) ? PCPPX_OK : PCPPX_E_INVAL;
+}
+
+int bpf_validate_all(const pcppx_bpf_prog* progs, uint32_t n_progs)
+{
+	if (progs == nullptr || n_progs == 0 || n_progs > PCPPX_BPF_MAX_PROGRAMS)
+		return PCPPX_E_INVAL;
+	for (uint32_t q = 0; q < n_progs; ++q)
+		if (progs[q].reserved != 0 || bpf_validate(progs[q].insns, progs[q].n_insns) != PCPPX_OK)
+			return PCPPX_E_INVAL;
+	return PCPPX_OK;
+}
+
+bool valid_bpf_io(const pcppx_batch* b, const pcppx_bpf_verdicts* o)
+{
+	if (b == nullptr || o == nullptr || o->totals == nullptr)
+		return false;
+	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+}
+
+uint32_t bpf_be(const uint8_t* p, uint32_t size)
+{
+	uint32_t v = 0;
+	for (uint32_t j = 0; j < size; ++j)
+		v = (v << 8) | p[j];
+	return v;
+}
+
+// one validated program over one packet: bpf_filter's result
+uint32_t bpf_run(const pcppx_bpf_insn* insns, uint32_t n, const uint8_t* p, uint32_t buflen, uint32_t wirelen)
+{
+	uint32_t A = 0, X = 0, M[PCPPX_BPF_MEMWORDS] = {};
+	for (uint32_t pc = 0; pc < n;)
+	{
+		const pcppx_bpf_insn& in = insns[pc++];
+		const uint32_t k = in.k;
+		const uint16_t c = in.code, cls = c & 0x07;
+		if (cls == kBpfLd || cls == kBpfLdx)
+		{
+			const uint16_t mode = c & 0xe0;
+			uint32_t v;
+			if (mode == kBpfImm)
+				v = k;
+			else if (mode == kBpfMem)
+				v = M[k];
+			else if (mode == kBpfLen)
+				v = wirelen;
+			else
+			{
+				const uint32_t size = (c & 0x18) == kBpfLdW ? 4 : (c & 0x18) == kBpfLdH ? 2 : 1;
+				const uint32_t x = mode == kBpfInd ? X : 0;
+				if (k > buflen || x > buflen - k || size > buflen - (x + k))
+					return 0;
+				v = bpf_be(p + x + k, size);
+				if (mode == kBpfMsh)
+					v = (v & 0xf) << 2;
+			}
+			(cls == kBpfLdx ? X : A) = v;
+		}
+		else if (cls == kBpfSt)
+			M[k] = A;
+		else if (cls == kBpfStx)
+			M[k] = X;
+		else if (cls == kBpfAlu)
+		{
+			const uint32_t s = (c & 0x08) ? X : k;
+			switch (c & 0xf0)
+			{
+			case kBpfAdd: A += s; break;
+			case kBpfSub: A -= s; break;
+			case kBpfMul: A *= s; break;
+			case kBpfDiv:
+				if (s == 0)
+					return 0;
+				A /= s;
+				break;
+			case kBpfMod:
+				if (s == 0)
+					return 0;
+				A %= s;
+				break;
+			case kBpfOr: A |= s; break;
+			case kBpfAnd: A &= s; break;
+			case kBpfXor: A ^= s; break;
+			case kBpfLsh: A = s < 32 ? A << s : 0; break;
+			case kBpfRsh: A = s < 32 ? A >> s : 0; break;
+			default: A = 0u - A; break;  // NEG
+			}
+		}
+		else if (cls == kBpfJmp)
+		{
+			const uint32_t s = (c & 0x08) ? X : k;
+			const uint16_t op = c & 0xf0;
+			if (op == kBpfJa)
+				pc += k;
+			else
+			{
+				const bool t = op == kBpfJeq ? A == s : op == kBpfJgt ? A > s : op == kBpfJge ? A >= s : (A & s) != 0;
+				pc += t ? in.jt : in.jf;
+			}
+		}
+		else if (cls == kBpfRet)
+			return (c & 0x18) == kBpfA ? A : k;
+		else if ((c & 0xf8) == kBpfTxa)
+			A = X;
+		else
+			X = A;
+	}
+	return 0;  // not reached by a validated program (its last instruction is a RET)
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_bpf_validate(const pcppx_bpf_insn* insns, uint32_t n_insns)
+	{
+		return bpf_validate(insns, n_insns);
+	}
+
+	int pcppx_bpf_load(pcppx_ctx* c, const pcppx_bpf_prog* progs, uint32_t n_progs, pcppx_bpf** out)
+	{
+		if (c == nullptr || out == nullptr || bpf_validate_all(progs, n_progs) != PCPPX_OK)
+			return PCPPX_E_INVAL;
+		*out = nullptr;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		pcppx_bpf* f = new (std::nothrow) pcppx_bpf;
+		if (f == nullptr)
+			return PCPPX_E_NOMEM;
+		f->device = c->device;
+		f->progs.n_progs = n_progs;
+		std::vector<pcppx_bpf_insn> all;
+		for (uint32_t q = 0; q < n_progs; ++q)
+		{
+			f->progs.start[q] = (uint32_t)all.size();
+			for (uint32_t i = 0; i < progs[q].n_insns; ++i)
+			{
+				const pcppx_bpf_insn& in = progs[q].insns[i];
+				if (in.code == (kBpfLd | kBpfMem) || in.code == (kBpfLdx | kBpfMem))
+					f->progs.uses_mem |= 1u << q;
+				all.push_back(in);
+			}
+		}
+		for (uint32_t q = n_progs; q <= PCPPX_BPF_MAX_PROGRAMS; ++q)
+			f->progs.start[q] = (uint32_t)all.size();
+		int rc = PCPPX_OK;
+		if (!ok(hipMalloc(reinterpret_cast<void**>(&f->d_insns), all.size() * sizeof(pcppx_bpf_insn))))
+			rc = PCPPX_E_NOMEM;
+		else if (!ok(hipMemcpy(f->d_insns, all.data(), all.size() * sizeof(pcppx_bpf_insn), hipMemcpyHostToDevice)) ||
+		         !ok(hipEventCreateWithFlags(&f->used, hipEventDisableTiming)))
+			rc = PCPPX_E_HIP;
+		if (rc != PCPPX_OK)
+		{
+			pcppx_bpf_free(f);
+			return rc;
+		}
+		f->progs.insns = f->d_insns;
+		*out = f;
+		return PCPPX_OK;
+	}
+
+	void pcppx_bpf_free(pcppx_bpf* f)
+	{
+		if (f == nullptr)
+			return;
+		(void)hipSetDevice(f->device);
+		if (f->pending)
+			(void)hipEventSynchronize(f->used);
+		if (f->d_insns)
+			(void)hipFree(f->d_insns);
+		if (f->used)
+			(void)hipEventDestroy(f->used);
+		delete f;
+	}
+
+	int pcppx_bpf_device(pcppx_ctx* c, const pcppx_bpf* f, const pcppx_batch* b, const uint32_t* frame_lens,
+	                     pcppx_bpf_verdicts* o, void* hip_stream)
+	{
+		if (c == nullptr || f == nullptr || !valid_bpf_io(b, o))
+			return PCPPX_E_INVAL;
+		if (f->device != c->device)
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (!ok(hipMemsetAsync(o->totals, 0, PCPPX_BPF_TOTALS * sizeof(uint64_t), st)))
+			return PCPPX_E_HIP;
+		if (b->n == 0)
+			return PCPPX_OK;
+		const int rc = pcppx::launch_bpf(b, frame_lens, f->progs, o, st);
+		if (rc != PCPPX_OK)
+			return rc;
+		// the handle's own bookkeeping, not the programs: free waits for the last launch that reads them
+		pcppx_bpf* h = const_cast<pcppx_bpf*>(f);
+		if (!ok(hipEventRecord(h->used, st)))
+			return PCPPX_E_HIP;
+		h->pending = true;
+		return PCPPX_OK;
+	}
+
+	int pcppx_bpf_reference(const pcppx_bpf_prog* progs, uint32_t n_progs, const pcppx_batch* b, const uint32_t* frame_lens,
+	                        pcppx_bpf_verdicts* o)
+	{
+		if (bpf_validate_all(progs, n_progs) != PCPPX_OK || !valid_bpf_io(b, o))
+			return PCPPX_E_INVAL;
+		uint64_t n_matched = 0, n_bad = 0;
+		for (uint32_t i = 0; i < b->n; ++i)
+		{
+			uint8_t matched = 0, bucket = 0xFF;
+			uint32_t ret = 0;
+			const uint64_t off = b->offsets[i];
+			const uint32_t cap = b->caplens[i];
+			if (off + cap < off || off + cap > b->data_len)
+				++n_bad;
+			else
+			{
+				const uint32_t wirelen = frame_lens != nullptr ? frame_lens[i] : cap;
+				for (uint32_t q = 0; q < n_progs && !matched; ++q)
+				{
+					const uint32_t r = bpf_run(progs[q].insns, progs[q].n_insns, b->data + off, cap, wirelen);
+					if (r != 0)
+					{
+						matched = 1;
+						bucket = (uint8_t)q;
+						ret = r;
+					}
+				}
+				n_matched += matched;
+			}
+			if (o->matched != nullptr)
+				o->matched[i] = matched;
+			if (o->bucket != nullptr)
+				o->bucket[i] = bucket;
+			if (o->ret != nullptr)
+				o->ret[i] = ret;
+		}
+		for (int k = 0; k < PCPPX_BPF_TOTALS; ++k)
+			o->totals[k] = 0;
+		o->totals[PCPPX_BPF_MATCHED] = n_matched;
+		o->totals[PCPPX_BPF_BAD_DESC] = n_bad;
+		return PCPPX_OK;
+	}
+}

@@ -55,4 +55,16 @@ uint32_t steer_blocks(uint32_t n);
 uint64_t steer_scratch_bytes(uint32_t n, uint32_t n_buckets);
 int launch_steer(const pcppx_batch* b, const pcppx_steer_spec* spec, const pcppx_steering* out, void* scratch,
                  hipStream_t stream);
+// pcppx_bpf_device (pcppx_bpf.hip): one launch on `stream` (the caller has cleared out->totals on it). insns: the
+// validated programs back to back in device memory; program p is insns[start[p] .. start[p + 1]); uses_mem: bit p set
+// when program p loads from M[] (only then are its slots cleared). Arguments are checked by the caller; n > 0.
+struct BpfPrograms
+{
+	const pcppx_bpf_insn* insns;
+	uint32_t n_progs;
+	uint32_t uses_mem;
+	uint32_t start[PCPPX_BPF_MAX_PROGRAMS + 1];
+};
+int launch_bpf(const pcppx_batch* b, const uint32_t* frame_lens, const BpfPrograms& progs, const pcppx_bpf_verdicts* out,
+               hipStream_t stream);
 }  // namespace pcppx

@@ -186,6 +186,27 @@ class Engine:
         abi.check(self.lib.pcppx_steer_device(self.ctx, C.byref(b), C.byref(spec), C.byref(out),
                                               C.c_void_p(stream or 0)), "pcppx_steer_device")
 
+    def bpf_load(self, programs) -> "BpfFilter":
+        """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
+        pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
+        progs, keep = abi.make_bpf_progs(programs)
+        h = C.c_void_p()
+        abi.check(self.lib.pcppx_bpf_load(self.ctx, progs, len(keep), C.byref(h)), "pcppx_bpf_load")
+        return BpfFilter(self.lib, h, len(keep))
+
+    def bpf_device(self, flt: "BpfFilter", data, offsets, caplens, n: int, linktype: int, totals, matched=None,
+                   bucket=None, ret=None, frame_lens=None, stream: int | None = None,
+                   data_len: int | None = None) -> None:
+        """Queue pcppx_bpf_device over device tensors: flt's programs run over every packet; matched (u8) / bucket (u8:
+        the first accepting program, 0xFF = none) / ret (i32: its return value) of n entries, each optional; totals:
+        8 x i64 (abi.BPF_*), overwritten; frame_lens: i32 wire lengths (None: the caplens). Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        out = abi.BpfVerdicts(opt(matched), opt(bucket), opt(ret), abi.ptr(totals))
+        abi.check(self.lib.pcppx_bpf_device(self.ctx, flt.handle, C.byref(b), opt(frame_lens), C.byref(out),
+                                            C.c_void_p(stream or 0)), "pcppx_bpf_device")
+
     def filter_reset(self, capacity: int = 0) -> None:
         abi.check(self.lib.pcppx_filter_reset(self.ctx, capacity), "pcppx_filter_reset")
 
@@ -201,6 +222,31 @@ class Engine:
 
     def sync(self) -> None:
         abi.check(self.lib.pcppx_sync(self.ctx), "pcppx_sync")
+
+
+class BpfFilter:
+    """Validated BPF programs resident on an engine's GPU (a pcppx_bpf handle, from Engine.bpf_load)."""
+
+    def __init__(self, lib, handle, n_programs: int):
+        self.lib, self.handle, self.n_programs = lib, handle, n_programs
+
+    def free(self) -> None:
+        """pcppx_bpf_free: waits for queued work that uses the programs."""
+        if self.handle:
+            self.lib.pcppx_bpf_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class PcapReader:
@@ -491,6 +537,31 @@ def steer_on_device(eng: Engine, batch: PacketBatch, bucket=None, key=None, key_
     if batch.frame_lens is not None:
         out.frame_lens = batch.frame_lens[index]
     return out, index, first.cpu().numpy().view(np.uint32), pos.cpu().numpy().view(np.uint64), tot
+
+
+def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
+    """Copy a host batch to HBM, run the classic BPF programs over its packets there (pcppx_bpf_device), copy the
+    verdicts back: (matched u8[n], bucket u8[n] = the first accepting program or 0xFF, ret u32[n] = its return value,
+    totals dict). programs: 1..16 programs in load order (pcapplusplus_amd.bpf); frame_lens: u32 wire lengths for
+    LD|LEN (None: the batch's frame_lens if it has them, else the caplens)."""
+    import torch
+
+    n = batch.n
+    if frame_lens is None:
+        frame_lens = batch.frame_lens
+    data, offsets, caplens = to_device(batch, device)
+    fl = None if frame_lens is None else \
+        torch.from_numpy(np.ascontiguousarray(frame_lens, dtype=np.uint32).view(np.int32)).to(device)
+    matched = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    bucket = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    ret = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    totals = torch.empty(abi.BPF_TOTALS, dtype=torch.int64, device=device)
+    with eng.bpf_load(programs) as flt:
+        eng.bpf_device(flt, data, offsets, caplens, n, batch.linktype, totals, matched, bucket, ret, fl,
+                       torch.cuda.current_stream(device).cuda_stream)
+        torch.cuda.synchronize(device)
+    return (matched[:n].cpu().numpy(), bucket[:n].cpu().numpy(), ret[:n].cpu().numpy().view(np.uint32),
+            abi.bpf_totals_dict(totals.cpu().numpy().view(np.uint64)))
 
 
 def bucket_batch(out: PacketBatch, bucket_first, b: int) -> PacketBatch:
