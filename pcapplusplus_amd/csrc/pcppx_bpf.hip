@@ -22,6 +22,7 @@
 
 #include "pcppx.h"
 #include "pcppx_internal.h"
+#include "pcppx_move.h"
 
 namespace pcppx
 {
@@ -111,10 +112,7 @@ __global__ __launch_bounds__(kBpfThreads) void bpf_kernel(BpfIn p, BpfPrograms f
 		bool bad = false;
 		if (in)
 		{
-			off = p.offsets[i];
-			buflen = p.caplens[i];
-			const uint64_t end = off + buflen;
-			bad = end < off || end > p.data_len;
+			bad = move::out_of_bounds(p.offsets, p.caplens, p.data_len, 0, i, off, buflen);
 			wirelen = p.frame_lens != nullptr ? p.frame_lens[i] : buflen;
 		}
 		const bool live = in && !bad;

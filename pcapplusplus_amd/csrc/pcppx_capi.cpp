@@ -20,6 +20,11 @@
 
 namespace
 {
+bool ok(hipError_t e)
+{
+	return e == hipSuccess;
+}
+
 constexpr size_t kChunkBytes = 64u << 20;    // packet bytes per host-path chunk
 constexpr uint32_t kChunkPackets = 1u << 18;  // packets per host-path chunk
 
@@ -150,6 +155,62 @@ private:
 
 constexpr uint32_t kDefaultFlowSlots = 1u << 22;  // 64 MiB of flow table in HBM
 constexpr uint32_t kMaxSlots = 3;                   // host-path chunk slots in flight
+
+// Stream-ordered scratch owned by a context and shared by its calls, with an event after each call's last kernel: the
+// next call (on whatever stream) waits for it on its own stream before touching the scratch, and a larger size is
+// reallocated in stream order behind that wait -- calls on one context are ordered even across streams, and no call
+// stalls the device or another stream.
+struct Scratch
+{
+	void* ptr = nullptr;
+	uint64_t bytes = 0;
+	hipEvent_t done = nullptr;
+	bool pending = false;
+
+	// at least `want` bytes for work on st, behind the previous user
+	int acquire(hipStream_t st, uint64_t want)
+	{
+		if (done == nullptr && !ok(hipEventCreateWithFlags(&done, hipEventDisableTiming)))
+			return PCPPX_E_HIP;
+		if (pending && !ok(hipStreamWaitEvent(st, done, 0)))
+			return PCPPX_E_HIP;
+		if (bytes < want)
+		{
+			if (ptr != nullptr && !ok(hipFreeAsync(ptr, st)))
+				return PCPPX_E_HIP;
+			ptr = nullptr;
+			bytes = 0;
+			if (!ok(hipMallocAsync(&ptr, want, st)))
+				return PCPPX_E_NOMEM;
+			bytes = want;
+		}
+		return PCPPX_OK;
+	}
+	// after the call's last kernel on st
+	int mark_used(hipStream_t st)
+	{
+		if (!ok(hipEventRecord(done, st)))
+			return PCPPX_E_HIP;
+		pending = true;
+		return PCPPX_OK;
+	}
+	// teardown, in this order: the last user is done; the memory goes back on st; the event goes
+	void wait() const
+	{
+		if (pending)
+			(void)hipEventSynchronize(done);
+	}
+	void release(hipStream_t st) const
+	{
+		if (ptr)
+			(void)hipFreeAsync(ptr, st);
+	}
+	void destroy_event() const
+	{
+		if (done)
+			(void)hipEventDestroy(done);
+	}
+};
 }  // namespace
 
 struct pcppx_ctx
@@ -166,30 +227,17 @@ struct pcppx_ctx
 	pcppx_packet_stats* d_stats = nullptr;
 	uint32_t flow_slots = 0;
 	uint64_t seq = 0;
-	// pcppx_flow_count_device: the partitioned flush's record queues and queue lengths (zero between calls), and
-	// an event after each call's last kernel: the next call (on whatever stream) waits for it before touching
-	// the scratch, so calls on one context are ordered even across streams
-	void* d_flow_queues = nullptr;
-	uint64_t flow_queue_recs = 0;
+	// pcppx_flow_count_device: the partitioned flush's record queues (16-B records) and, allocated apart, the queue
+	// lengths (zero between calls)
+	Scratch flow;
 	uint32_t* d_flow_fill = nullptr;
-	hipEvent_t flow_done = nullptr;
-	bool flow_pending = false;
 	// pcppx_records.proto_stats: the parse's per-wave collectStats records (16 B per 64 packets), summed into the
-	// caller's counters by a second kernel; ordered across calls like the flow scratch
-	void* d_wave_stats = nullptr;
-	uint64_t wave_stats_bytes = 0;
-	hipEvent_t stats_done = nullptr;
-	bool stats_pending = false;
-	// pcppx_select_device: the per-block sums and bases (28 B per 256 packets), ordered across calls like the flow scratch
-	void* d_select = nullptr;
-	uint64_t select_bytes = 0;
-	hipEvent_t select_done = nullptr;
-	bool select_pending = false;
-	// pcppx_steer_device: the block sums per bucket and the bucket totals (steer_scratch_bytes), ordered likewise
-	void* d_steer = nullptr;
-	uint64_t steer_bytes = 0;
-	hipEvent_t steer_done = nullptr;
-	bool steer_pending = false;
+	// caller's counters by a second kernel
+	Scratch stats;
+	// pcppx_select_device: the per-block sums and bases (28 B per kSelectBlockPk packets)
+	Scratch select;
+	// pcppx_steer_device: the block sums per bucket and the bucket totals (steer_scratch_bytes)
+	Scratch steer;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -206,11 +254,6 @@ struct pcppx_ctx
 
 namespace
 {
-bool ok(hipError_t e)
-{
-	return e == hipSuccess;
-}
-
 // ---- the engine's header window (PCPPX_WINDOW_DEFAULT) ----
 constexpr unsigned long long kWinMinSample = 2048;  // sampled packets per decision (a launch samples up to ~4096)
 constexpr unsigned long long kWinDeepShare = 256;   // deep stacks above 1 in 256 sampled packets: deep traffic
@@ -315,28 +358,6 @@ bool valid_device_records(const pcppx_opts* o, const pcppx_records* r)
 	return o->layout != PCPPX_LAYOUT_DENSE;  // DENSE: the host path's layout
 }
 
-// Scratch owned by a context and shared by its calls: a call waits (on its own stream) for the previous call's
-// `done` event before touching it, and a larger size is reallocated in stream order behind that wait -- no call
-// stalls the device or another stream.
-int ensure_scratch(hipStream_t st, void** ptr, uint64_t* have, uint64_t want, hipEvent_t* done, bool pending)
-{
-	if (*done == nullptr && !ok(hipEventCreateWithFlags(done, hipEventDisableTiming)))
-		return PCPPX_E_HIP;
-	if (pending && !ok(hipStreamWaitEvent(st, *done, 0)))
-		return PCPPX_E_HIP;
-	if (*have < want)
-	{
-		if (*ptr != nullptr && !ok(hipFreeAsync(*ptr, st)))
-			return PCPPX_E_HIP;
-		*ptr = nullptr;
-		*have = 0;
-		if (!ok(hipMallocAsync(ptr, want, st)))
-			return PCPPX_E_NOMEM;
-		*have = want;
-	}
-	return PCPPX_OK;
-}
-
 // launch a device parse (plain or with the fused reassembly output) with the collectStats reduction when
 // r->proto_stats is set
 int device_parse(pcppx_ctx* c, const pcppx_batch* b, const pcppx_opts* o, pcppx_records* r, pcppx_reasm_info* info,
@@ -345,11 +366,10 @@ int device_parse(pcppx_ctx* c, const pcppx_batch* b, const pcppx_opts* o, pcppx_
 	void* ws = nullptr;
 	if (r->proto_stats != nullptr)
 	{
-		const int rc = ensure_scratch(st, &c->d_wave_stats, &c->wave_stats_bytes, (uint64_t)pcppx::parse_waves(b->n) * 16,
-		                              &c->stats_done, c->stats_pending);
+		const int rc = c->stats.acquire(st, (uint64_t)pcppx::parse_waves(b->n) * 16);
 		if (rc != PCPPX_OK)
 			return rc;
-		ws = c->d_wave_stats;
+		ws = c->stats.ptr;
 	}
 	const pcppx_opts eo = resolve_window(c, o);
 	unsigned long long* win = window_sample(c, o);
@@ -359,12 +379,7 @@ int device_parse(pcppx_ctx* c, const pcppx_batch* b, const pcppx_opts* o, pcppx_
 	if (rc != PCPPX_OK || ws == nullptr)
 		return rc;
 	rc = pcppx::launch_proto_stats_reduce(ws, b->n, r->proto_stats, st);
-	if (rc != PCPPX_OK)
-		return rc;
-	if (!ok(hipEventRecord(c->stats_done, st)))
-		return PCPPX_E_HIP;
-	c->stats_pending = true;
-	return PCPPX_OK;
+	return rc != PCPPX_OK ? rc : c->stats.mark_used(st);
 }
 
 void free_slot(Slot& s)
@@ -886,25 +901,17 @@ extern "C"
 			free_slot(s);
 		}
 		free_filter(c);
-		if (c->flow_pending)
-			(void)hipEventSynchronize(c->flow_done);
-		if (c->stats_pending)
-			(void)hipEventSynchronize(c->stats_done);
-		// the flow / stats scratch is stream-ordered memory (hipMallocAsync): released on the context's stream
-		if (c->d_flow_queues)
-			(void)hipFreeAsync(c->d_flow_queues, c->stream);
+		// the scratch is stream-ordered memory (hipMallocAsync): released on the context's stream
+		c->flow.wait();
+		c->stats.wait();
+		c->flow.release(c->stream);
 		if (c->d_flow_fill)
 			(void)hipFreeAsync(c->d_flow_fill, c->stream);
-		if (c->d_wave_stats)
-			(void)hipFreeAsync(c->d_wave_stats, c->stream);
-		if (c->select_pending)
-			(void)hipEventSynchronize(c->select_done);
-		if (c->d_select)
-			(void)hipFreeAsync(c->d_select, c->stream);
-		if (c->steer_pending)
-			(void)hipEventSynchronize(c->steer_done);
-		if (c->d_steer)
-			(void)hipFreeAsync(c->d_steer, c->stream);
+		c->stats.release(c->stream);
+		c->select.wait();
+		c->select.release(c->stream);
+		c->steer.wait();
+		c->steer.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -915,14 +922,8 @@ extern "C"
 			(void)hipFree(c->d_win);
 			(void)hipHostFree(c->h_win);
 		}
-		if (c->flow_done)
-			(void)hipEventDestroy(c->flow_done);
-		if (c->stats_done)
-			(void)hipEventDestroy(c->stats_done);
-		if (c->select_done)
-			(void)hipEventDestroy(c->select_done);
-		if (c->steer_done)
-			(void)hipEventDestroy(c->steer_done);
+		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer })
+			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
 	}
@@ -1138,12 +1139,8 @@ int flow_count(pcppx_ctx* c, const pcppx_summary* summary, const uint32_t* keys_
 		hipStream_t st = static_cast<hipStream_t>(hip_stream);
 		const uint32_t parts = pcppx::flow_partitions(capacity);
 		const uint32_t rec_cap = pcppx::flow_queue_capacity(n, capacity);
-		// the context's previous flow work (possibly queued on another stream) owns the scratch until flow_done; a
-		// larger one is allocated in stream order behind that wait
-		uint64_t have = c->flow_queue_recs * 16;
-		const int src = ensure_scratch(st, &c->d_flow_queues, &have, (uint64_t)parts * rec_cap * 16, &c->flow_done,
-		                               c->flow_pending);
-		c->flow_queue_recs = have / 16;
+		// the context's previous flow work (possibly queued on another stream) owns the queues until it is done
+		const int src = c->flow.acquire(st, (uint64_t)parts * rec_cap * 16);
 		if (src != PCPPX_OK)
 			return src;
 		if (c->d_flow_fill == nullptr)
@@ -1153,13 +1150,8 @@ int flow_count(pcppx_ctx* c, const pcppx_summary* summary, const uint32_t* keys_
 				return PCPPX_E_NOMEM;
 		}
 		const int rc = pcppx::launch_flow_count_part(summary, keys_in, caplens, n, keys, packets, bytes, capacity, stats,
-		                                             c->d_flow_queues, rec_cap, c->d_flow_fill, st);
-		if (rc != PCPPX_OK)
-			return rc;
-		if (!ok(hipEventRecord(c->flow_done, st)))
-			return PCPPX_E_HIP;
-		c->flow_pending = true;
-		return PCPPX_OK;
+		                                             c->flow.ptr, rec_cap, c->d_flow_fill, st);
+		return rc != PCPPX_OK ? rc : c->flow.mark_used(st);
 	}
 }
 
@@ -1225,6 +1217,25 @@ extern "C"
 
 namespace
 {
+// a device-batch operator's batch (non-null): empty, or with descriptors and, unless data_len is 0, bytes
+bool valid_batch(const pcppx_batch* b)
+{
+	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+}
+
+// The descriptor rule, as the host references apply it (the kernels': move::out_of_bounds in pcppx_move.h): packet i is
+// out of bounds (true) when offsets[i] + caplens[i] wraps or exceeds data_len; else off = its source offset and
+// len = min(caplen, snaplen), snaplen 0 = no limit.
+bool out_of_bounds(const pcppx_batch* b, uint32_t snaplen, uint32_t i, uint64_t& off, uint32_t& len)
+{
+	off = b->offsets[i];
+	const uint32_t cap = b->caplens[i];
+	if (off + cap < off || off + cap > b->data_len)
+		return true;
+	len = (snaplen != 0 && cap > snaplen) ? snaplen : cap;
+	return false;
+}
+
 // the argument rules pcppx_select_device and pcppx_select_reference share (include/pcppx.h)
 bool valid_select(const pcppx_batch* b, const pcppx_select_spec* s, const pcppx_selection* o)
 {
@@ -1237,7 +1248,7 @@ bool valid_select(const pcppx_batch* b, const pcppx_select_spec* s, const pcppx_
 		return false;
 	if (s->invert > 1 || s->reserved != 0 || s->reserved2 != 0 || o->reserved != 0)
 		return false;
-	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+	return valid_batch(b);
 }
 }  // namespace
 
@@ -1253,18 +1264,12 @@ extern "C"
 		hipStream_t st = static_cast<hipStream_t>(hip_stream);
 		if (b->n == 0)
 			return ok(hipMemsetAsync(o->totals, 0, PCPPX_SEL_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous select (possibly queued on another stream) owns the block sums until select_done
-		int rc = ensure_scratch(st, &c->d_select, &c->select_bytes, pcppx::select_scratch_bytes(b->n), &c->select_done,
-		                        c->select_pending);
+		// the context's previous select (possibly queued on another stream) owns the block sums until it is done
+		int rc = c->select.acquire(st, pcppx::select_scratch_bytes(b->n));
 		if (rc != PCPPX_OK)
 			return rc;
-		rc = pcppx::launch_select(b, s, o, c->d_select, st);
-		if (rc != PCPPX_OK)
-			return rc;
-		if (!ok(hipEventRecord(c->select_done, st)))
-			return PCPPX_E_HIP;
-		c->select_pending = true;
-		return PCPPX_OK;
+		rc = pcppx::launch_select(b, s, o, c->select.ptr, st);
+		return rc != PCPPX_OK ? rc : c->select.mark_used(st);
 	}
 
 	int pcppx_select_reference(const pcppx_batch* b, const pcppx_select_spec* s, pcppx_selection* o)
@@ -1286,14 +1291,13 @@ extern "C"
 			}
 			if (chosen == (s->invert != 0))
 				continue;
-			const uint64_t off = b->offsets[i];
-			const uint32_t cap = b->caplens[i];
-			if (off + cap < off || off + cap > b->data_len)
+			uint64_t off;
+			uint32_t len;
+			if (out_of_bounds(b, s->snaplen, i, off, len))
 			{
 				++bad;
 				continue;
 			}
-			const uint32_t len = (s->snaplen != 0 && cap > s->snaplen) ? s->snaplen : cap;
 			open = open && sel < o->max_packets && (o->data == nullptr || sel_bytes + len <= o->data_cap);
 			if (open)
 			{
@@ -1337,7 +1341,7 @@ bool valid_steer(const pcppx_batch* b, const pcppx_steer_spec* s, const pcppx_st
 		return false;
 	if (s->reserved != 0 || o->reserved != 0)
 		return false;
-	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+	return valid_batch(b);
 }
 }  // namespace
 
@@ -1357,18 +1361,12 @@ extern "C"
 			               ok(hipMemsetAsync(o->bucket_pos, 0, (s->n_buckets + 1) * sizeof(uint64_t), st))
 			           ? PCPPX_OK
 			           : PCPPX_E_HIP;
-		// the context's previous steer (possibly queued on another stream) owns the block sums until steer_done
-		int rc = ensure_scratch(st, &c->d_steer, &c->steer_bytes, pcppx::steer_scratch_bytes(b->n, s->n_buckets),
-		                        &c->steer_done, c->steer_pending);
+		// the context's previous steer (possibly queued on another stream) owns the block sums until it is done
+		int rc = c->steer.acquire(st, pcppx::steer_scratch_bytes(b->n, s->n_buckets));
 		if (rc != PCPPX_OK)
 			return rc;
-		rc = pcppx::launch_steer(b, s, o, c->d_steer, st);
-		if (rc != PCPPX_OK)
-			return rc;
-		if (!ok(hipEventRecord(c->steer_done, st)))
-			return PCPPX_E_HIP;
-		c->steer_pending = true;
-		return PCPPX_OK;
+		rc = pcppx::launch_steer(b, s, o, c->steer.ptr, st);
+		return rc != PCPPX_OK ? rc : c->steer.mark_used(st);
 	}
 
 	int pcppx_steer_reference(const pcppx_batch* b, const pcppx_steer_spec* s, pcppx_steering* o)
@@ -1398,15 +1396,13 @@ extern "C"
 				++dropped;
 				continue;
 			}
-			const uint64_t off = b->offsets[i];
-			const uint32_t cap = b->caplens[i];
-			if (off + cap < off || off + cap > b->data_len)
+			uint64_t off;
+			if (out_of_bounds(b, s->snaplen, i, off, len[i]))
 			{
 				++bad;
 				continue;
 			}
 			bucket[i] = v;
-			len[i] = (s->snaplen != 0 && cap > s->snaplen) ? s->snaplen : cap;
 			++first[v + 1];
 			pos[v + 1] += len[i];
 		}
@@ -1567,7 +1563,7 @@ bool valid_bpf_io(const pcppx_batch* b, const pcppx_bpf_verdicts* o)
 {
 	if (b == nullptr || o == nullptr || o->totals == nullptr)
 		return false;
-	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+	return valid_batch(b);
 }
 
 uint32_t bpf_be(const uint8_t* p, uint32_t size)
@@ -1760,9 +1756,9 @@ extern "C"
 		{
 			uint8_t matched = 0, bucket = 0xFF;
 			uint32_t ret = 0;
-			const uint64_t off = b->offsets[i];
-			const uint32_t cap = b->caplens[i];
-			if (off + cap < off || off + cap > b->data_len)
+			uint64_t off;
+			uint32_t cap;
+			if (out_of_bounds(b, 0, i, off, cap))
 				++n_bad;
 			else
 			{

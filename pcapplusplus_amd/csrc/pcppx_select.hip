@@ -14,11 +14,13 @@
 
 #include "pcppx.h"
 #include "pcppx_internal.h"
+#include "pcppx_move.h"
 
 namespace pcppx
 {
 namespace
 {
+using namespace move;
 constexpr uint32_t kSelThreads = 256, kSelWaves = kSelThreads / 64;
 constexpr uint32_t kSelTilesPerWave = 4, kSelTiles = kSelWaves * kSelTilesPerWave;  // 64-packet tiles per wave / block
 static_assert(kSelTiles * 64 == kSelectBlockPk, "a block gathers kSelectBlockPk packets");
@@ -64,32 +66,12 @@ __device__ __forceinline__ void classify(const SelIn& p, uint64_t i, bool& sel, 
 	                        : (*reinterpret_cast<const uint16_t*>(p.flags + i * p.flags_stride) & p.flags_any) != 0;
 	if (chosen == (p.invert != 0))
 		return;
-	off = p.offsets[i];
-	const uint32_t cap = p.caplens[i];
-	const uint64_t end = off + cap;
-	if (end < off || end > p.data_len)
+	if (out_of_bounds(p.offsets, p.caplens, p.data_len, p.snaplen, i, off, len))
 	{
 		bad = true;
 		return;
 	}
-	len = (p.snaplen != 0 && cap > p.snaplen) ? p.snaplen : cap;
 	sel = true;
-}
-
-__device__ __forceinline__ uint64_t wave_scan_incl(uint64_t v, uint32_t lane)
-{
-	for (uint32_t o = 1; o < 64; o <<= 1)
-	{
-		const uint64_t t = __shfl_up(v, o);
-		v += lane >= o ? t : 0ull;
-	}
-	return v;
-}
-
-// the first packet of tile t (0 .. kSelTiles-1) of the block: wave w owns tiles 4w .. 4w+3
-__device__ __forceinline__ uint64_t tile_first(uint32_t t)
-{
-	return (uint64_t)blockIdx.x * kSelectBlockPk + t * 64;
 }
 
 __global__ __launch_bounds__(kSelThreads) void select_count_kernel(SelIn p, uint64_t* __restrict__ bbytes,
@@ -107,13 +89,12 @@ __global__ __launch_bounds__(kSelThreads) void select_count_kernel(SelIn p, uint
 		bool sel, bad;
 		uint32_t len;
 		uint64_t off;
-		classify(p, tile_first(w * kSelTilesPerWave + u) + lane, sel, bad, len, off);
+		classify(p, tile_first(kSelectBlockPk, w * kSelTilesPerWave + u) + lane, sel, bad, len, off);
 		b += len;
 		c += __popcll(__ballot(sel));
 		d += __popcll(__ballot(bad));
 	}
-	for (int o = 32; o > 0; o >>= 1)
-		b += __shfl_xor(b, o);
+	b = wave_sum(b);
 	if (lane == 0)
 	{
 		lb[w] = b;
@@ -185,8 +166,7 @@ __global__ __launch_bounds__(64) void select_base_kernel(uint32_t g, const uint6
 		run_b += __shfl(ib, 63);
 		run_c += __shfl(ic, 63);
 	}
-	for (int o = 32; o > 0; o >>= 1)
-		bad += __shfl_xor(bad, o);
+	bad = wave_sum(bad);
 	if (lane == 0)
 	{
 		totals[PCPPX_SEL_SELECTED_PACKETS] = run_c;
@@ -196,32 +176,6 @@ __global__ __launch_bounds__(64) void select_base_kernel(uint32_t g, const uint6
 		totals[PCPPX_SEL_BAD_DESC] = bad;
 		totals[5] = totals[6] = totals[7] = 0;
 	}
-}
-
-// bytes sh .. sh+15 of the 32 bytes a:b
-__device__ __forceinline__ uint4 funnel16(uint4 a, uint4 b, uint32_t sh)
-{
-	uint32_t w0 = a.x, w1 = a.y, w2 = a.z, w3 = a.w, w4 = b.x, w5 = b.y;
-	if (sh & 8)
-	{
-		w0 = a.z;
-		w1 = a.w;
-		w2 = b.x;
-		w3 = b.y;
-		w4 = b.z;
-		w5 = b.w;
-	}
-	if (sh & 4)
-	{
-		w0 = w1;
-		w1 = w2;
-		w2 = w3;
-		w3 = w4;
-		w4 = w5;
-	}
-	const uint32_t s = sh & 3;
-	return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, s), __builtin_amdgcn_alignbyte(w2, w1, s),
-	                  __builtin_amdgcn_alignbyte(w3, w2, s), __builtin_amdgcn_alignbyte(w4, w3, s));
 }
 
 // the packet that holds position lo (qS <= lo < qE) of a tile's span: the last k < nw with dq[k] <= lo (dq ascending,
@@ -324,10 +278,8 @@ __global__ __launch_bounds__(kSelThreads) void select_copy_kernel(SelIn p, SelOu
 		bool sel, bad;
 		uint32_t len;
 		uint64_t off;
-		classify(p, tile_first(w * kSelTilesPerWave + u) + lane, sel, bad, len, off);
-		uint64_t b = len;
-		for (int x = 32; x > 0; x >>= 1)
-			b += __shfl_xor(b, x);
+		classify(p, tile_first(kSelectBlockPk, w * kSelTilesPerWave + u) + lane, sel, bad, len, off);
+		const uint64_t b = wave_sum(len);
 		const uint32_t c = __popcll(__ballot(sel));
 		if (lane == 0)
 		{
@@ -344,10 +296,8 @@ __global__ __launch_bounds__(kSelThreads) void select_copy_kernel(SelIn p, SelOu
 		tile_rank += s_tc[t];
 	}
 	const bool copy = o.data != nullptr;
-	const uint32_t dal = (uint32_t)(reinterpret_cast<uintptr_t>(o.data) & 15);
-	uint8_t* const dbase = o.data - dal;  // 16-B aligned; position q (= byte position + dal) lives at dbase + q
-	const uint32_t sal = (uint32_t)(reinterpret_cast<uintptr_t>(p.data) & 15);
-	const uint8_t* const sbase = p.data - sal;  // the same for source positions (= batch offset + sal)
+	const auto [dbase, dal] = align16(o.data);  // position q (= byte position + dal) lives at dbase + q
+	const auto [sbase, sal] = align16(p.data);  // the same for source positions (= batch offset + sal)
 	uint64_t* const dq = s_dq[w];
 	uint64_t* const sa = s_src[w];
 
@@ -355,7 +305,7 @@ __global__ __launch_bounds__(kSelThreads) void select_copy_kernel(SelIn p, SelOu
 	for (uint32_t u = 0; u < kSelTilesPerWave; ++u)
 	{
 		const uint32_t t = w * kSelTilesPerWave + u;
-		const uint64_t i = tile_first(t) + lane;
+		const uint64_t i = tile_first(kSelectBlockPk, t) + lane;
 		bool sel, bad;
 		uint32_t len;
 		uint64_t off;

@@ -20,11 +20,13 @@
 
 #include "pcppx.h"
 #include "pcppx_internal.h"
+#include "pcppx_move.h"
 
 namespace pcppx
 {
 namespace
 {
+using namespace move;
 constexpr uint32_t kStThreads = 256, kStWaves = kStThreads / 64;
 constexpr uint32_t kStTilesPerWave = 4;
 static_assert(kStWaves * kStTilesPerWave * 64 == kSteerBlockPk, "a block steers kSteerBlockPk packets");
@@ -77,39 +79,12 @@ __device__ __forceinline__ uint32_t classify(const StIn& p, uint64_t i, bool& dr
 		drop = true;
 		return kNoBucket;
 	}
-	off = p.offsets[i];
-	const uint32_t cap = p.caplens[i];
-	const uint64_t end = off + cap;
-	if (end < off || end > p.data_len)
+	if (out_of_bounds(p.offsets, p.caplens, p.data_len, p.snaplen, i, off, len))
 	{
 		bad = true;
 		return kNoBucket;
 	}
-	len = (p.snaplen != 0 && cap > p.snaplen) ? p.snaplen : cap;
 	return v;
-}
-
-__device__ __forceinline__ uint64_t wave_scan_incl(uint64_t v, uint32_t lane)
-{
-	for (uint32_t o = 1; o < 64; o <<= 1)
-	{
-		const uint64_t t = __shfl_up(v, o);
-		v += lane >= o ? t : 0ull;
-	}
-	return v;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
-{
-	for (int o = 32; o > 0; o >>= 1)
-		v += __shfl_xor(v, o);
-	return v;
-}
-
-// the first packet of tile t (0 .. 15) of the block: wave w owns tiles 4w .. 4w+3
-__device__ __forceinline__ uint64_t tile_first(uint32_t t)
-{
-	return (uint64_t)blockIdx.x * kSteerBlockPk + t * 64;
 }
 
 // cnt / bytes: rows of g block sums, row k = bucket k
@@ -134,7 +109,7 @@ __global__ __launch_bounds__(kStThreads) void steer_count_kernel(StIn p, uint32_
 		bool drop, bad;
 		uint32_t len;
 		uint64_t off;
-		const uint32_t b = classify(p, tile_first(w * kStTilesPerWave + u) + lane, drop, bad, len, off);
+		const uint32_t b = classify(p, tile_first(kSteerBlockPk, w * kStTilesPerWave + u) + lane, drop, bad, len, off);
 		if (b != kNoBucket)  // sums: the order in which the adds land does not show
 		{
 			atomicAdd(&s_c[b], 1u);
@@ -242,32 +217,6 @@ __global__ __launch_bounds__(64) void steer_bases_kernel(uint32_t g, uint32_t K,
 	}
 }
 
-// bytes sh .. sh+15 of the 32 bytes a:b
-__device__ __forceinline__ uint4 funnel16(uint4 a, uint4 b, uint32_t sh)
-{
-	uint32_t w0 = a.x, w1 = a.y, w2 = a.z, w3 = a.w, w4 = b.x, w5 = b.y;
-	if (sh & 8)
-	{
-		w0 = a.z;
-		w1 = a.w;
-		w2 = b.x;
-		w3 = b.y;
-		w4 = b.z;
-		w5 = b.w;
-	}
-	if (sh & 4)
-	{
-		w0 = w1;
-		w1 = w2;
-		w2 = w3;
-		w3 = w4;
-		w4 = w5;
-	}
-	const uint32_t s = sh & 3;
-	return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, s), __builtin_amdgcn_alignbyte(w2, w1, s),
-	                  __builtin_amdgcn_alignbyte(w3, w2, s), __builtin_amdgcn_alignbyte(w4, w3, s));
-}
-
 // the packet (lane number) that owns whole chunk c of the tile's flattened list: the last k <= 63 with cp[k] <= c (cp:
 // the exclusive prefix of the packets' whole-chunk counts, ascending; c < cp[64]). Packets without a whole chunk ahead
 // of it are passed over; branch-free.
@@ -346,7 +295,7 @@ __global__ __launch_bounds__(kStThreads) void steer_copy_kernel(StIn p, StOut o,
 		bool drop, bad;
 		uint32_t len;
 		uint64_t off;
-		const uint32_t b = classify(p, tile_first(w * kStTilesPerWave + u) + lane, drop, bad, len, off);
+		const uint32_t b = classify(p, tile_first(kSteerBlockPk, w * kStTilesPerWave + u) + lane, drop, bad, len, off);
 		if (b != kNoBucket)
 		{
 			atomicAdd(&s_rc[w][b], 1u);
@@ -372,10 +321,8 @@ __global__ __launch_bounds__(kStThreads) void steer_copy_kernel(StIn p, StOut o,
 	}
 	__syncthreads();
 	const bool copy = o.data != nullptr;
-	const uint32_t dal = (uint32_t)(reinterpret_cast<uintptr_t>(o.data) & 15);
-	uint8_t* const dbase = o.data - dal;  // 16-B aligned; position q (= byte position + dal) lives at dbase + q
-	const uint32_t sal = (uint32_t)(reinterpret_cast<uintptr_t>(p.data) & 15);
-	const uint8_t* const sbase = p.data - sal;  // the same for source positions (= batch offset + sal)
+	const auto [dbase, dal] = align16(o.data);  // position q (= byte position + dal) lives at dbase + q
+	const auto [sbase, sal] = align16(p.data);  // the same for source positions (= batch offset + sal)
 	uint64_t* const cp = s_cp[w];
 	uint64_t* const dq = s_dq[w];
 	uint64_t* const sa = s_sa[w];
@@ -383,7 +330,7 @@ __global__ __launch_bounds__(kStThreads) void steer_copy_kernel(StIn p, StOut o,
 #pragma unroll 1
 	for (uint32_t u = 0; u < kStTilesPerWave; ++u)
 	{
-		const uint64_t i = tile_first(w * kStTilesPerWave + u) + lane;
+		const uint64_t i = tile_first(kSteerBlockPk, w * kStTilesPerWave + u) + lane;
 		bool drop, bad;
 		uint32_t len;
 		uint64_t off;

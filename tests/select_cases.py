@@ -9,73 +9,36 @@ touched.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field, replace
+from dataclasses import dataclass, replace
 
 import numpy as np
 
+import mover_cases as mc
+from mover_cases import FILL, PAD_BYTES, PAD_ENTRIES, mix_lens, packed  # noqa: F401  (the tests read them here)
 from pcapplusplus_amd import abi
 
-FILL = 0xA5
-PAD_BYTES, PAD_ENTRIES = 64, 4
 BLOCK = 1024  # packets per block of the count and copy kernels (pcppx_internal.h kSelectBlockPk)
 BASE_STEP = 256  # block sums per step of select_base_kernel's scan (one wave, four consecutive blocks per lane)
 SCAN3_N = 2 * BASE_STEP * BLOCK + 1029  # two whole steps of that scan, then a block and a partial one
+FIELDS = ("offsets", "caplens", "index", "data")
 
 
 @dataclass
-class Case:
-    name: str
-    data: np.ndarray      # u8
-    offsets: np.ndarray   # u64
-    caplens: np.ndarray   # u32
+class Case(mc.Case):
     keep: np.ndarray | None = None    # u8[n]; None = flags mode
     flags: np.ndarray | None = None   # flags mode: the records' bytes (u8, n * flags_stride)
     flags_stride: int = 0
     flags_any: int = 0
     invert: bool = False
-    snaplen: int = 0
-    data_len: int | None = None       # None: len(data)
-    data_cap: int | None = None       # None: the bytes of the whole batch (always enough)
-    max_packets: int | None = None    # None: n
-    index_only: bool = False
-    want_index: bool = True
-    out_misalign: int = 0             # device runs: out->data starts this many bytes past a 16-B boundary
-    meta: dict = field(default_factory=dict)
-
-    @property
-    def n(self) -> int:
-        return len(self.caplens)
-
-    def dlen(self) -> int:
-        return len(self.data) if self.data_len is None else self.data_len
-
-    def cap(self) -> int:
-        if self.data_cap is not None:
-            return self.data_cap
-        dl = np.uint64(self.dlen())
-        room = dl - np.minimum(self.offsets, dl)  # no 64-bit wrap: the bytes from the offset to data_len
-        ok = (self.offsets <= dl) & (self.caplens.astype(np.uint64) <= room)  # the in-bounds packets
-        return int(self.caplens[ok].astype(np.uint64).sum())
-
-    def maxp(self) -> int:
-        return self.n if self.max_packets is None else self.max_packets
 
 
 @dataclass
-class Buffers:
-    data: np.ndarray | None
-    offsets: np.ndarray
-    caplens: np.ndarray
-    index: np.ndarray | None
+class Buffers(mc.Buffers):
     totals: np.ndarray
 
 
 def alloc(c: Case) -> Buffers:
-    return Buffers(None if c.index_only else np.full(c.cap() + PAD_BYTES, FILL, np.uint8),
-                   np.full(c.maxp() + PAD_ENTRIES, 0xA5A5A5A5A5A5A5A5, np.uint64),
-                   np.full(c.maxp() + PAD_ENTRIES, 0xA5A5A5A5, np.uint32),
-                   np.full(c.maxp() + PAD_ENTRIES, 0xA5A5A5A5, np.uint32) if c.want_index else None,
-                   np.full(abi.SEL_TOTALS, 0xA5A5A5A5A5A5A5A5, np.uint64))
+    return Buffers(*mc.alloc(c), np.full(abi.SEL_TOTALS, mc.F64, np.uint64))
 
 
 def chosen(c: Case) -> np.ndarray:
@@ -140,64 +103,25 @@ def run_reference(c: Case) -> Buffers:
 
 
 def run_device(engine, c: Case, device: str = "cuda:0", source=None) -> Buffers:
-    """source: (data, offsets, caplens, data_len) tensors already on the device to select from instead of c's own batch
-    (c then holds the rule, the capacities and, for the runners on the host, the same packets in a small buffer)."""
+    """source: see mover_cases.Staged."""
     import torch
 
     host = alloc(c)
-    up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
-    if source is None:
-        data = up(c.data if len(c.data) else np.zeros(1, np.uint8))
-        offsets, caplens, data_len = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32)), c.dlen()
-    else:
-        data, offsets, caplens, data_len = source
+    dev = mc.Staged(c, host, device, source)
     rule = np.ascontiguousarray(c.keep if c.keep is not None else c.flags)
-    rule_t = up(rule if len(rule) else np.zeros(16, np.uint8))
-    mis = c.out_misalign
-    d_raw = None if c.index_only else up(np.concatenate([np.full(16 + mis, FILL, np.uint8), host.data]))
-    d_data = None if c.index_only else d_raw[16 + mis:]
-    if d_data is not None:
-        assert d_data.data_ptr() % 16 == mis
-    d_off, d_cap = up(host.offsets.view(np.int64)), up(host.caplens.view(np.int32))
-    d_idx = up(host.index.view(np.int32)) if host.index is not None else None
-    d_tot = up(host.totals.view(np.int64))
-    engine.select_device(data, offsets, caplens, c.n, 1, _spec(c, abi.ptr(rule_t), abi.ptr(rule_t)), d_off, d_cap,
-                         d_tot, c.maxp(), d_data, c.cap(), d_idx, torch.cuda.current_stream(device).cuda_stream,
-                         data_len=data_len)
-    torch.cuda.synchronize(device)
-    if d_raw is not None:  # the bytes in front of out->data belong to someone else
-        assert bool((d_raw[:16 + mis] == FILL).all()), "bytes before out->data were written"
-    dn = lambda t, dt: t.cpu().numpy().view(dt)  # noqa: E731
-    return Buffers(None if d_data is None else dn(d_data, np.uint8), dn(d_off, np.uint64), dn(d_cap, np.uint32),
-                   None if d_idx is None else dn(d_idx, np.uint32), dn(d_tot, np.uint64))
+    rule_t = dev.up(rule if len(rule) else np.zeros(16, np.uint8))
+    d_tot = dev.up(host.totals.view(np.int64))
+    engine.select_device(dev.data, dev.offsets, dev.caplens, c.n, 1, _spec(c, abi.ptr(rule_t), abi.ptr(rule_t)),
+                         dev.d_off, dev.d_cap, d_tot, c.maxp(), dev.d_data, c.cap(), dev.d_idx,
+                         torch.cuda.current_stream(device).cuda_stream, data_len=dev.data_len)
+    return Buffers(*dev.common(), dev.down(d_tot, np.uint64))
 
 
 def assert_same(got: Buffers, want: Buffers, what: str) -> None:
-    """Whole buffers, pads included: the written part equal, the 0xA5 fill intact everywhere else."""
-    assert list(got.totals) == list(want.totals), (what, "totals", list(got.totals), list(want.totals))
-    for f in ("offsets", "caplens", "index", "data"):
-        g, w = getattr(got, f), getattr(want, f)
-        assert (g is None) == (w is None), (what, f)
-        if g is None:
-            continue
-        assert g.shape == w.shape, (what, f, g.shape, w.shape)
-        bad = np.nonzero(g != w)[0]
-        assert len(bad) == 0, (what, f, len(bad), "first at", int(bad[0]), int(g[bad[0]]), int(w[bad[0]]))
+    mc.assert_same(got, want, what, FIELDS)
 
 
 # ------------------------------------------------------------------ generators
-def packed(lens, seed: int, start: int = 0, gaps=None, tail: int = 0):
-    """Packets of the given lengths, back to back from byte `start` (gaps[i] unused bytes ahead of packet i); `tail`
-    unused bytes after the last one (0: it ends exactly at data_len). Bytes are random, so a wrong source shows."""
-    lens = np.asarray(lens, dtype=np.uint32)
-    g = np.zeros(len(lens), np.uint64) if gaps is None else np.asarray(gaps, dtype=np.uint64)
-    step = lens.astype(np.uint64) + g
-    offs = np.uint64(start) + np.cumsum(step) - lens.astype(np.uint64) if len(lens) else np.zeros(0, np.uint64)
-    total = int(start + step.sum()) + tail
-    data = np.random.default_rng(seed).integers(0, 256, total, dtype=np.uint8)
-    return data, offs.astype(np.uint64), lens
-
-
 def mask(n: int, pattern: str, seed: int = 0) -> np.ndarray:
     k = np.zeros(n, np.uint8)
     rng = np.random.default_rng(seed)
@@ -217,10 +141,6 @@ def mask(n: int, pattern: str, seed: int = 0) -> np.ndarray:
         k[:64] = 1
         k[128:192] = 1
     return k
-
-
-def mix_lens(n: int, hi: int, seed: int) -> np.ndarray:
-    return np.random.default_rng(seed).integers(0, hi + 1, n).astype(np.uint32)
 
 
 def make(name: str, lens, pattern: str = "p50", seed: int = 1, **kw) -> Case:
@@ -265,15 +185,9 @@ def cases() -> list[Case]:
     for s in range(16):
         out.append(make(f"start{s}", mix_lens(200, 100, 20 + s), "p50", seed=20 + s, start=s))
     out.append(make("gapped", mix_lens(600, 200, 40), "p50", seed=40, gaps=mix_lens(600, 40, 41)))
-    c = make("shuffled", mix_lens(600, 200, 42), "p50", seed=42)
-    perm = np.random.default_rng(43).permutation(c.n)
-    out.append(replace(c, offsets=c.offsets[perm], caplens=c.caplens[perm]))
-    c = make("overlap", mix_lens(300, 200, 44), "all", seed=44)
-    twice = np.repeat(np.arange(c.n), 2)  # two descriptors over the same bytes ...
-    offs, lens = c.offsets[twice].copy(), c.caplens[twice].copy()
-    offs[1::2] += np.minimum(lens[1::2], 3)  # ... the second one starting inside the first
-    lens[1::2] -= np.minimum(lens[1::2], 3)
-    out.append(replace(c, offsets=offs, caplens=lens, keep=mask(len(lens), "p50", 45)))
+    out.append(mc.shuffled(make("shuffled", mix_lens(600, 200, 42), "p50", seed=42), 43))
+    c = mc.overlapped(make("overlap", mix_lens(300, 200, 44), "all", seed=44))
+    out.append(replace(c, keep=mask(c.n, "p50", 45)))
     for mis in (1, 7, 15):  # a destination that does not start on a 16-B boundary
         out.append(make(f"dst_misaligned{mis}", mix_lens(400, 150, 46 + mis), "p50", seed=46 + mis, out_misalign=mis))
     # snaplen
@@ -290,20 +204,8 @@ def cases() -> list[Case]:
                    ("index_only", dict(index_only=True)), ("index_only_cap_ignored", dict(index_only=True, data_cap=5)),
                    ("index_only_maxp", dict(index_only=True, max_packets=sp // 3)), ("no_index", dict(want_index=False))):
         out.append(replace(base, name=nm, **kw))
-    # bad descriptors mixed in: past the end, a huge caplen, an offset whose end wraps 64 bits
     for pat in ("all", "p50"):
-        c = make(f"bad_desc_{pat}", mix_lens(900, 120, 70), pat, seed=70)
-        offs, lens = c.offsets.copy(), c.caplens.copy()
-        offs[5::37] = len(c.data) - 1
-        lens[5::37] = np.maximum(lens[5::37], 2)
-        lens[11::53] = 0xFFFFFFF0
-        offs[17::101] = np.uint64(0xFFFFFFFFFFFFFFF0)
-        lens[17::101] = 64
-        offs[64] = len(c.data)  # an empty packet at the very end is in bounds ...
-        lens[64] = 0
-        offs[65] = len(c.data)  # ... one byte there is not
-        lens[65] = 1
-        out.append(replace(c, offsets=offs, caplens=lens))
+        out.append(mc.with_bad_descriptors(make(f"bad_desc_{pat}", mix_lens(900, 120, 70), pat, seed=70)))
     # flags mode over synthetic records (the device tests also run it over a real parse's records)
     for stride in (16, 32):
         c = make(f"flags_stride{stride}", mix_lens(800, 150, 80), "none", seed=80)

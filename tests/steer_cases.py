@@ -9,57 +9,28 @@ touched, and nothing at all on overflow.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field, replace
+from dataclasses import dataclass, replace
 
 import numpy as np
 
+import mover_cases as mc
+from mover_cases import F32, F64, FILL, mix_lens, packed
 from pcapplusplus_amd import abi
-from select_cases import FILL, PAD_BYTES, PAD_ENTRIES, SCAN3_N, mix_lens, packed
+from select_cases import SCAN3_N
 
 BLOCK = 1024    # packets per block of the count and copy kernels (pcppx_internal.h kSteerBlockPk)
 SCAN_STEP = 64  # block sums per step of the per-bucket scan (pcppx_internal.h kSteerScanStep)
 BUCKET_STEP = 64  # buckets per step of the one-wave bucket-base scan (one per lane)
-F32, F64 = 0xA5A5A5A5, 0xA5A5A5A5A5A5A5A5
 
 
 @dataclass
-class Case:
-    name: str
-    data: np.ndarray      # u8
-    offsets: np.ndarray   # u64
-    caplens: np.ndarray   # u32
+class Case(mc.Case):
     n_buckets: int = 1
     bucket: np.ndarray | None = None  # u8[n]; None = key mode
     key: np.ndarray | None = None     # key mode: the records' bytes (u8, n * key_stride), the key at key_offset
     key_stride: int = 4
     key_offset: int = 0
-    snaplen: int = 0
-    data_len: int | None = None       # None: len(data)
-    data_cap: int | None = None       # None: the bytes of the whole batch (always enough)
-    max_packets: int | None = None    # None: n
-    index_only: bool = False
-    want_index: bool = True
-    out_misalign: int = 0             # device runs: out->data starts this many bytes past a 16-B boundary
-    src_misalign: int = 0             # device runs: batch->data likewise
-    meta: dict = field(default_factory=dict)
-
-    @property
-    def n(self) -> int:
-        return len(self.caplens)
-
-    def dlen(self) -> int:
-        return len(self.data) if self.data_len is None else self.data_len
-
-    def cap(self) -> int:
-        if self.data_cap is not None:
-            return self.data_cap
-        dl = np.uint64(self.dlen())
-        room = dl - np.minimum(self.offsets, dl)  # no 64-bit wrap: the bytes from the offset to data_len
-        ok = (self.offsets <= dl) & (self.caplens.astype(np.uint64) <= room)  # the in-bounds packets
-        return int(self.caplens[ok].astype(np.uint64).sum())
-
-    def maxp(self) -> int:
-        return self.n if self.max_packets is None else self.max_packets
+    src_misalign: int = 0             # device runs: batch->data starts this many bytes past a 16-B boundary
 
     def keys(self) -> np.ndarray:
         """Key mode: the n 32-bit keys."""
@@ -74,11 +45,7 @@ class Case:
 
 
 @dataclass
-class Buffers:
-    data: np.ndarray | None
-    offsets: np.ndarray
-    caplens: np.ndarray
-    index: np.ndarray | None
+class Buffers(mc.Buffers):
     bucket_first: np.ndarray
     bucket_pos: np.ndarray
     totals: np.ndarray
@@ -88,13 +55,8 @@ FIELDS = ("offsets", "caplens", "index", "bucket_first", "bucket_pos", "data")
 
 
 def alloc(c: Case) -> Buffers:
-    return Buffers(None if c.index_only else np.full(c.cap() + PAD_BYTES, FILL, np.uint8),
-                   np.full(c.maxp() + PAD_ENTRIES, F64, np.uint64),
-                   np.full(c.maxp() + PAD_ENTRIES, F32, np.uint32),
-                   np.full(c.maxp() + PAD_ENTRIES, F32, np.uint32) if c.want_index else None,
-                   np.full(c.n_buckets + 1 + PAD_ENTRIES, F32, np.uint32),
-                   np.full(c.n_buckets + 1 + PAD_ENTRIES, F64, np.uint64),
-                   np.full(abi.STEER_TOTALS, F64, np.uint64))
+    return Buffers(*mc.alloc(c), np.full(c.n_buckets + 1 + mc.PAD_ENTRIES, F32, np.uint32),
+                   np.full(c.n_buckets + 1 + mc.PAD_ENTRIES, F64, np.uint64), np.full(abi.STEER_TOTALS, F64, np.uint64))
 
 
 def brute(c: Case) -> Buffers:
@@ -161,37 +123,16 @@ def run_reference(c: Case) -> Buffers:
     return out
 
 
-class DeviceRun:
+class DeviceRun(mc.Staged):
     """A case's tensors on the device; launch() queues pcppx_steer_device on a stream, result() reads the buffers."""
 
     def __init__(self, c: Case, device: str = "cuda:0", source=None):
-        """source: (data, offsets, caplens, data_len) tensors already on the device to steer from instead of c's own
-        batch (c then holds the rule, the capacities and, for the runners on the host, the same packets in a small
-        buffer)."""
-        import torch
-
-        self.c, self.device = c, device
+        """source: see mover_cases.Staged."""
         host = alloc(c)
-        up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
-        if source is None:
-            src = c.data if len(c.data) else np.zeros(1, np.uint8)
-            self.s_raw = up(np.concatenate([np.zeros(16 + c.src_misalign, np.uint8), src]))
-            self.data = self.s_raw[16 + c.src_misalign:]
-            assert self.data.data_ptr() % 16 == c.src_misalign
-            self.offsets, self.caplens = up(c.offsets.view(np.int64)), up(c.caplens.view(np.int32))
-            self.data_len = c.dlen()
-        else:
-            self.data, self.offsets, self.caplens, self.data_len = source
-        self.rule = up(_rule(c))
-        mis = c.out_misalign
-        self.d_raw = None if c.index_only else up(np.concatenate([np.full(16 + mis, FILL, np.uint8), host.data]))
-        self.d_data = None if c.index_only else self.d_raw[16 + mis:]
-        if self.d_data is not None:
-            assert self.d_data.data_ptr() % 16 == mis
-        self.d_off, self.d_cap = up(host.offsets.view(np.int64)), up(host.caplens.view(np.int32))
-        self.d_idx = up(host.index.view(np.int32)) if host.index is not None else None
-        self.d_first, self.d_pos = up(host.bucket_first.view(np.int32)), up(host.bucket_pos.view(np.int64))
-        self.d_tot = up(host.totals.view(np.int64))
+        super().__init__(c, host, device, source, c.src_misalign)
+        self.rule = self.up(_rule(c))
+        self.d_first, self.d_pos = self.up(host.bucket_first.view(np.int32)), self.up(host.bucket_pos.view(np.int64))
+        self.d_tot = self.up(host.totals.view(np.int64))
 
     def launch(self, engine, stream: int) -> None:
         c = self.c
@@ -200,16 +141,8 @@ class DeviceRun:
                             stream, data_len=self.data_len)
 
     def result(self) -> Buffers:
-        import torch
-
-        torch.cuda.synchronize(self.device)
-        mis = self.c.out_misalign
-        if self.d_raw is not None:  # the bytes in front of out->data belong to someone else
-            assert bool((self.d_raw[:16 + mis] == FILL).all()), "bytes before out->data were written"
-        dn = lambda t, dt: t.cpu().numpy().view(dt)  # noqa: E731
-        return Buffers(None if self.d_data is None else dn(self.d_data, np.uint8), dn(self.d_off, np.uint64),
-                       dn(self.d_cap, np.uint32), None if self.d_idx is None else dn(self.d_idx, np.uint32),
-                       dn(self.d_first, np.uint32), dn(self.d_pos, np.uint64), dn(self.d_tot, np.uint64))
+        return Buffers(*self.common(), self.down(self.d_first, np.uint32), self.down(self.d_pos, np.uint64),
+                       self.down(self.d_tot, np.uint64))
 
 
 def run_device(engine, c: Case, device: str = "cuda:0", source=None) -> Buffers:
@@ -221,16 +154,7 @@ def run_device(engine, c: Case, device: str = "cuda:0", source=None) -> Buffers:
 
 
 def assert_same(got: Buffers, want: Buffers, what: str) -> None:
-    """Whole buffers, pads included: the written part equal, the 0xA5 fill intact everywhere else."""
-    assert list(got.totals) == list(want.totals), (what, "totals", list(got.totals), list(want.totals))
-    for f in FIELDS:
-        g, w = getattr(got, f), getattr(want, f)
-        assert (g is None) == (w is None), (what, f)
-        if g is None:
-            continue
-        assert g.shape == w.shape, (what, f, g.shape, w.shape)
-        bad = np.nonzero(g != w)[0]
-        assert len(bad) == 0, (what, f, len(bad), "first at", int(bad[0]), int(g[bad[0]]), int(w[bad[0]]))
+    mc.assert_same(got, want, what, FIELDS)
 
 
 def assert_untouched(got: Buffers, what: str) -> None:
@@ -380,29 +304,12 @@ def cases() -> list[Case]:
     # source layout: gaps, unordered and overlapping descriptors; `tail` 0 everywhere, so the last packet ends exactly at
     # data_len
     out.append(make("gapped", mix_lens(600, 200, 40), 8, "random", seed=40, gaps=mix_lens(600, 40, 41)))
-    c = make("shuffled", mix_lens(600, 200, 42), 8, "random", seed=42)
-    perm = np.random.default_rng(43).permutation(c.n)
-    out.append(replace(c, offsets=c.offsets[perm], caplens=c.caplens[perm]))
-    c = make("overlap", mix_lens(300, 200, 44), 8, "random", seed=44)
-    twice = np.repeat(np.arange(c.n), 2)  # two descriptors over the same bytes ...
-    offs, lens2 = c.offsets[twice].copy(), c.caplens[twice].copy()
-    offs[1::2] += np.minimum(lens2[1::2], 3)  # ... the second one starting inside the first
-    lens2[1::2] -= np.minimum(lens2[1::2], 3)
-    out.append(replace(c, offsets=offs, caplens=lens2, bucket=column(len(lens2), 8, "random", 45)))
-    # bad descriptors, inside steered buckets and inside dropped ones: past the end, a huge caplen, an end that wraps
+    out.append(mc.shuffled(make("shuffled", mix_lens(600, 200, 42), 8, "random", seed=42), 43))
+    c = mc.overlapped(make("overlap", mix_lens(300, 200, 44), 8, "random", seed=44))
+    out.append(replace(c, bucket=column(c.n, 8, "random", 45)))
+    # bad descriptors, inside steered buckets and inside dropped ones
     for K, pat in ((8, "random"), (5, "some_dropped"), (8, "all_dropped")):
-        c = make(f"bad_desc_{pat}_k{K}", mix_lens(900, 120, 70), K, pat, seed=70)
-        offs, lens2 = c.offsets.copy(), c.caplens.copy()
-        offs[5::37] = len(c.data) - 1
-        lens2[5::37] = np.maximum(lens2[5::37], 2)
-        lens2[11::53] = 0xFFFFFFF0
-        offs[17::101] = np.uint64(0xFFFFFFFFFFFFFFF0)
-        lens2[17::101] = 64
-        offs[64] = len(c.data)  # an empty packet at the very end is in bounds ...
-        lens2[64] = 0
-        offs[65] = len(c.data)  # ... one byte there is not
-        lens2[65] = 1
-        out.append(replace(c, offsets=offs, caplens=lens2))
+        out.append(mc.with_bad_descriptors(make(f"bad_desc_{pat}_k{K}", mix_lens(900, 120, 70), K, pat, seed=70)))
     # snaplen below, at and above the packet sizes
     for sn in (1, 14, 60, 64, 200, 5000):
         out.append(make(f"snap{sn}", mix_lens(500, 200, 50), 8, "random", seed=50, snaplen=sn))
