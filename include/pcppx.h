@@ -532,6 +532,126 @@ PCPPX_API int pcppx_steer_device(pcppx_ctx* ctx, const pcppx_batch* batch, const
 /* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
 PCPPX_API int pcppx_steer_reference(const pcppx_batch* batch, const pcppx_steer_spec* spec, pcppx_steering* out);
 
+/* ---- defrag: reassemble the IPv4 fragment groups that are complete inside one device batch (IPDefragUtil) ----
+ * pcppx_reasm_device stops at the fragment table; this is the table's common case, for packets that sit in HBM:
+ * what Examples/IPDefragUtil does with IPReassembly::processPacket (Packet++/src/IPReassembly.cpp:281-515). Fragment
+ * groups that are complete and well formed inside the batch are reassembled on the device into an ordinary
+ * pcppx_batch (parse it again: the datagram gets its L4 layer, hash5 and checksums); every other fragment is labelled
+ * and left for the caller's host IPReassembly. Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * Inputs: a device batch, its records from a device parse (FIXED layout, max_layers >= 1, the same max_layers here; the
+ * summary or, when it is NULL, the brief supplies n_layers; PACKED records are refused as in pcppx_reasm_device) and
+ * info[n], the pcppx_reasm_info of the same batch. info is an input column: it is not recomputed, and any info is legal.
+ *
+ * Candidates: packet i is a candidate iff (info[i].ip_status & 15) == PCPPX_IPR_FRAGMENT, PCPPX_IPR_F_IPV6 is not set,
+ * its descriptor is in bounds (the rule of select and steer: offsets[i] + caplens[i] <= data_len, the 64-bit wrap
+ * checked) and its chain records an IPv4 layer: the first layer of protocol IPv4 among the first
+ * min(n_layers, max_layers) entries, the one IPv4FragmentWrapper takes (IPReassembly.cpp:71-74). Then
+ * ip_off = layer.offset, hdr = layer.hdr_len and len = layer.data_len - layer.hdr_len (getIPLayerPayloadSize(): a
+ * trailer is excluded). The layer must lie inside the packet (hdr >= 20, hdr <= data_len, offset + data_len <= caplen:
+ * always so for the records of a parse of this batch; records that say otherwise are never followed outside the
+ * packet). A FRAGMENT packet without such a layer is not a candidate (it is LEFT).
+ *
+ * Groups: all candidates with the same ip_key. The 32-bit hash alone decides, exactly as m_FragmentMap is keyed by the
+ * hash alone (IPReassembly.cpp:322-327). frag_offset and PCPPX_IPR_F_LAST are taken from info.
+ *
+ * Clean groups: sort a group by (frag_offset, source index). It is reassembled iff it has 2..PCPPX_DEFRAG_MAX_FRAGS
+ * members, every len > 0, member k's frag_offset equals the sum of the len of the members before it (an exact tiling
+ * from 0: no gap, overlap or duplicate), exactly the sorted-last member has PCPPX_IPR_F_LAST,
+ * ip_off + hdr + total <= PCPPX_MAX_CAPLEN (ip_off / hdr: the first member's; total: the sum of the len) and
+ * hdr + total <= 65535. For such a group the reference returns the same packet whatever order the members arrive in,
+ * and returns it when the last one arrives: until the member at offset 0 arrives every other member has
+ * frag_offset > currentOffset = 0 and is parked in the out-of-order list (processPacket :425-446); the member at
+ * offset 0 allocates the packet from its own bytes (:355-376); from then on currentOffset is always the end of a
+ * tiling prefix, so an arriving member either continues it (:394-423) or is parked, and matchOutOfOrderFragments
+ * (:640-701) appends the parked members in offset order. Nothing is appended twice or dropped (no member is below
+ * currentOffset, the duplicate path of :447-453), and gotLastFragment is raised exactly when the LAST member is
+ * appended, which needs every member before it: on the arrival of the member with the highest source index. A group
+ * that fails the rule is order-dependent or needs the host's duplicate handling: it stays with the host.
+ *
+ * The reassembled packet (IPReassembly.cpp:364-372, 409-415, 463-487; IPv4Layer.cpp:372-413): bytes
+ * [0, ip_off + hdr + len) of the first member (its trailer dropped), then the payloads of the other members in offset
+ * order; in the IP header at ip_off, bytes 2-3 = be16(hdr + total), bytes 6-7 = 0 (fragmentOffset = 0 clears DF too) and
+ * bytes 10-11 = the header checksum over hdr bytes with the field zeroed. The protocol byte does not change:
+ * computeCalculateFields rewrites it only to the value parseNextLayer dispatched on to build that next layer.
+ *
+ * Output, in source order: a reassembled packet takes the slot of its group's member with the highest source index
+ * (where processPacket returns REASSEMBLED and IPDefragUtil writes it); the other members produce nothing. With
+ * spec->passthrough = 1 every other in-bounds packet (non-fragments, HOST packets, IPv6 fragments, LEFT fragments) is
+ * copied unchanged in place: IPDefragUtil's output file. With passthrough = 0 only the reassembled packets come out. */
+#define PCPPX_DEFRAG_MAX_FRAGS 64
+typedef struct pcppx_defrag_spec {
+	uint32_t max_fragments; /* the candidates the call has room for; 0 = n (always enough) */
+	uint8_t passthrough;    /* 0 / 1 */
+	uint8_t reserved[3];
+} pcppx_defrag_spec;
+
+/* pcppx_defragged.disposition values */
+#define PCPPX_DEFRAG_PASS 0        /* not an IPv4 fragment (in bounds) */
+#define PCPPX_DEFRAG_LEFT 1        /* an IPv4 fragment of a group the device did not reassemble, or an IPv6 fragment:
+                                      the host table decides */
+#define PCPPX_DEFRAG_MERGED 2      /* merged into a reassembled packet */
+#define PCPPX_DEFRAG_MERGED_LAST 3 /* merged, and its output slot holds the packet */
+#define PCPPX_DEFRAG_BAD_DESC 4    /* the descriptor is out of bounds: never read, never copied */
+
+/* pcppx_defragged.totals words */
+#define PCPPX_DEFRAG_OUT_PACKETS 0
+#define PCPPX_DEFRAG_OUT_BYTES 1
+#define PCPPX_DEFRAG_REASSEMBLED 2  /* clean groups = reassembled packets */
+#define PCPPX_DEFRAG_MERGED_FRAGS 3 /* their members */
+#define PCPPX_DEFRAG_LEFT_FRAGS 4   /* packets with disposition LEFT */
+#define PCPPX_DEFRAG_CANDIDATES 5
+#define PCPPX_DEFRAG_BAD_DESC_N 6   /* packets with disposition BAD_DESC */
+#define PCPPX_DEFRAG_OVERFLOW 7
+#define PCPPX_DEFRAG_TOTALS 8
+
+typedef struct pcppx_defragged { /* all device pointers (host pointers for pcppx_defrag_reference) */
+	uint8_t* data;        /* packed bytes of the output packets, back to back, no padding; NULL = index-only */
+	uint64_t data_cap;
+	uint64_t* offsets;    /* max_packets entries */
+	uint32_t* caplens;    /* max_packets entries */
+	uint32_t* index;      /* optional (NULL): index[j] = source packet number; a reassembled packet: the completing
+	                         member's (strictly ascending) */
+	uint32_t* first;      /* optional (NULL): the source number of the member whose headers, and so whose timestamp,
+	                         packet j carries; a copied packet: index[j] */
+	uint8_t* frags;       /* optional (NULL): members merged into packet j; 0 = a copied packet */
+	uint8_t* disposition; /* optional (NULL): n entries, PCPPX_DEFRAG_* per source packet */
+	uint32_t max_packets;
+	uint32_t reserved;
+	uint64_t* totals;     /* PCPPX_DEFRAG_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_defragged;
+
+/* Capacity is all or nothing, as in steer: OVERFLOW = 1 iff OUT_PACKETS > max_packets, or data != NULL and
+ * OUT_BYTES > data_cap, or CANDIDATES > max_fragments (0 = n). Then only the totals are written (no byte of data, no
+ * entry of offsets / caplens / index / first / frags / disposition): they hold the full would-be values, except that
+ * with CANDIDATES > max_fragments the groups cannot be formed and only CANDIDATES, BAD_DESC_N and OVERFLOW are given
+ * (the other words are 0). max_packets = n, data_cap = the sum of the caplens and max_fragments = n always suffice: a
+ * reassembled packet is no longer than its members together (the first member's prefix plus the other members'
+ * payloads, each a part of its own packet). With data == NULL no bytes move, the byte capacity is not applied and
+ * offsets hold the would-be positions.
+ * As select and steer: a packet of any caplen is copied; the source may be gapped, unordered or overlapping;
+ * out->data must not overlap batch->data. Source bytes are read only through aligned 16-B granules that hold a byte of
+ * a packet that is emitted or merged. Nothing outside [0, OUT_BYTES) of data or past the first OUT_PACKETS entries of
+ * the per-output columns is written. The output is a pure function of the inputs, bit-identical from run to run:
+ * every output position comes from counts and scans; atomics only form sets and sums. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals, offsets or caplens; with n > 0 a
+ * null info, records->layers, or records->summary and records->brief both; PACKED (or DENSE) records; max_layers 0 or
+ * above PCPPX_MAX_LAYERS; passthrough above 1; a non-zero reserved field. The work is queued on hip_stream and the
+ * call returns without waiting; calls on one context are ordered through its defrag scratch (a buffer and an event of
+ * their own, as select's and steer's). Scratch: with g = ceil(n / 1024) blocks, F = min(max_fragments or n, n) and
+ * C = the power of two >= max(2F, 64): 16 + 40 g + 40 F + 40 C bytes (block sums and bases, one record per candidate,
+ * one group slot per table entry; the table is cleared by every call, so a max_fragments sized to the traffic saves
+ * time as well as memory); PCPPX_E_NOMEM when it cannot be allocated.
+ * The call is batch-local. A caller that keeps a host IPReassembly across batches must see that its table holds
+ * nothing for a key before trusting a reassembled packet of that key (an earlier batch may have left fragments of it
+ * there); the LEFT fragments are what it feeds that table. */
+PCPPX_API int pcppx_defrag_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                  uint8_t max_layers, const pcppx_reasm_info* info, const pcppx_defrag_spec* spec,
+                                  pcppx_defragged* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_defrag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                     const pcppx_reasm_info* info, const pcppx_defrag_spec* spec, pcppx_defragged* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

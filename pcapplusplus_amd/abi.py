@@ -219,6 +219,43 @@ def steer_reference(batch: Batch, spec: SteerSpec, out: Steering) -> None:
     check(load_engine().pcppx_steer_reference(C.byref(batch), C.byref(spec), C.byref(out)), "pcppx_steer_reference")
 
 
+# pcppx_defrag_*: the IPv4 fragment groups that are complete inside a batch (include/pcppx.h, defrag)
+DEFRAG_MAX_FRAGS = 64
+DEFRAG_PASS, DEFRAG_LEFT, DEFRAG_MERGED, DEFRAG_MERGED_LAST, DEFRAG_BAD_DESC = 0, 1, 2, 3, 4  # disposition values
+(DEFRAG_OUT_PACKETS, DEFRAG_OUT_BYTES, DEFRAG_REASSEMBLED, DEFRAG_MERGED_FRAGS, DEFRAG_LEFT_FRAGS, DEFRAG_CANDIDATES,
+ DEFRAG_BAD_DESC_N, DEFRAG_OVERFLOW) = range(8)  # pcppx_defragged.totals words
+DEFRAG_TOTALS = 8
+DEFRAG_FIELDS = ("out_packets", "out_bytes", "reassembled", "merged_frags", "left_frags", "candidates", "bad_desc",
+                 "overflow")
+
+
+class DefragSpec(C.Structure):
+    """pcppx_defrag_spec: the room for candidates (0 = n) and whether the other packets are copied through."""
+    _fields_ = [("max_fragments", C.c_uint32), ("passthrough", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class Defragged(C.Structure):
+    """pcppx_defragged: the packed output batch, its per-packet columns, the per-source disposition and the totals."""
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("offsets", C.c_void_p), ("caplens", C.c_void_p),
+                ("index", C.c_void_p), ("first", C.c_void_p), ("frags", C.c_void_p), ("disposition", C.c_void_p),
+                ("max_packets", C.c_uint32), ("reserved", C.c_uint32), ("totals", C.c_void_p)]
+
+
+def make_defrag_spec(passthrough: bool = True, max_fragments: int = 0) -> DefragSpec:
+    return DefragSpec(max_fragments, 1 if passthrough else 0)
+
+
+def defrag_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(DEFRAG_FIELDS)}
+
+
+def defrag_reference(batch: Batch, records: Records, max_layers: int, info, spec: DefragSpec, out: Defragged) -> None:
+    """pcppx_defrag_reference: pcppx_defrag_device's contract in plain C++ over host pointers (no GPU). info: the
+    address of n pcppx_reasm_info; the structs hold addresses of host (numpy) arrays the caller keeps alive."""
+    check(load_engine().pcppx_defrag_reference(C.byref(batch), C.byref(records), max_layers, info, C.byref(spec),
+                                               C.byref(out)), "pcppx_defrag_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -425,6 +462,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_steer_device.restype = C.c_int
     lib.pcppx_steer_reference.argtypes = [C.POINTER(Batch), C.POINTER(SteerSpec), C.POINTER(Steering)]
     lib.pcppx_steer_reference.restype = C.c_int
+    lib.pcppx_defrag_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P, C.POINTER(DefragSpec),
+                                        C.POINTER(Defragged), P]
+    lib.pcppx_defrag_device.restype = C.c_int
+    lib.pcppx_defrag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P, C.POINTER(DefragSpec),
+                                           C.POINTER(Defragged)]
+    lib.pcppx_defrag_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -451,6 +494,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_pcap_read_batch", "pcppx_pcap_read_batch_ex", "pcppx_pcap_map_batch", "pcppx_pcap_close", "pcppx_host_alloc", "pcppx_host_free",
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
+    "pcppx_defrag_device", "pcppx_defrag_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

@@ -6,10 +6,12 @@
 // on the CPU except the copy into pinned staging on the host path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <condition_variable>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -238,6 +240,8 @@ struct pcppx_ctx
 	Scratch select;
 	// pcppx_steer_device: the block sums per bucket and the bucket totals (steer_scratch_bytes)
 	Scratch steer;
+	// pcppx_defrag_device: the group table, the candidate records and the block sums (defrag_scratch_bytes)
+	Scratch defrag;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -912,6 +916,8 @@ extern "C"
 		c->select.release(c->stream);
 		c->steer.wait();
 		c->steer.release(c->stream);
+		c->defrag.wait();
+		c->defrag.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -922,7 +928,7 @@ extern "C"
 			(void)hipFree(c->d_win);
 			(void)hipHostFree(c->h_win);
 		}
-		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer })
+		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1441,6 +1447,240 @@ extern "C"
 				o->index[r] = i;
 			if (o->data != nullptr && len[i] != 0)
 				std::memcpy(o->data + p, b->data + b->offsets[i], len[i]);
+		}
+		return PCPPX_OK;
+	}
+}
+
+// ---- defrag: the IPv4 fragment groups that are complete inside a batch (include/pcppx.h, defrag) ----
+namespace
+{
+// the argument rules pcppx_defrag_device and pcppx_defrag_reference share (include/pcppx.h)
+bool valid_defrag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
+                  const pcppx_defrag_spec* s, const pcppx_defragged* o)
+{
+	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
+	    o->caplens == nullptr)
+		return false;
+	if (max_layers == 0 || max_layers > PCPPX_MAX_LAYERS || r->layout != PCPPX_LAYOUT_FIXED)
+		return false;
+	if (s->passthrough > 1 || s->reserved[0] != 0 || s->reserved[1] != 0 || s->reserved[2] != 0 || o->reserved != 0)
+		return false;
+	if (b->n != 0 && (info == nullptr || r->layers == nullptr || (r->summary == nullptr && r->brief == nullptr)))
+		return false;
+	return valid_batch(b);
+}
+
+// where the chain lengths are read from: the summary's n_layers, else the brief's
+const uint8_t* n_layers_column(const pcppx_records* r, uint32_t& stride)
+{
+	if (r->summary != nullptr)
+	{
+		stride = sizeof(pcppx_summary);
+		return &r->summary->n_layers;
+	}
+	stride = sizeof(pcppx_brief);
+	return &r->brief->n_layers;
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_defrag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                        const pcppx_reasm_info* info, const pcppx_defrag_spec* s, pcppx_defragged* o,
+	                        void* hip_stream)
+	{
+		if (c == nullptr || !valid_defrag(b, r, max_layers, info, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_DEFRAG_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous defrag (possibly queued on another stream) owns the table until it is done
+		int rc = c->defrag.acquire(st, pcppx::defrag_scratch_bytes(b->n, s->max_fragments));
+		if (rc != PCPPX_OK)
+			return rc;
+		uint32_t stride;
+		const uint8_t* nl = n_layers_column(r, stride);
+		rc = pcppx::launch_defrag(b, r->layers, max_layers, nl, stride, info, s, o, c->defrag.ptr, st);
+		return rc != PCPPX_OK ? rc : c->defrag.mark_used(st);
+	}
+
+	int pcppx_defrag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                           const pcppx_reasm_info* info, const pcppx_defrag_spec* s, pcppx_defragged* o)
+	{
+		if (!valid_defrag(b, r, max_layers, info, s, o))
+			return PCPPX_E_INVAL;
+		const uint32_t n = b->n;
+		struct Frag
+		{
+			uint32_t idx, foff, len, ip_off, hdr;
+			bool last;
+		};
+		// every packet's disposition; the candidates by key, in source order
+		std::vector<uint8_t> disp(n, PCPPX_DEFRAG_PASS);
+		std::map<uint32_t, std::vector<Frag>> groups;
+		uint64_t candidates = 0, bad = 0;
+		uint32_t stride = 0;
+		const uint8_t* nlc = n != 0 ? n_layers_column(r, stride) : nullptr;
+		for (uint32_t i = 0; i < n; ++i)
+		{
+			uint64_t off;
+			uint32_t cap;
+			if (out_of_bounds(b, 0, i, off, cap))
+			{
+				disp[i] = PCPPX_DEFRAG_BAD_DESC;
+				++bad;
+				continue;
+			}
+			const uint8_t st = info[i].ip_status;
+			if ((st & 15) != PCPPX_IPR_FRAGMENT)
+				continue;
+			disp[i] = PCPPX_DEFRAG_LEFT;  // until its group turns out clean
+			if (st & PCPPX_IPR_F_IPV6)
+				continue;
+			const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
+			for (uint32_t k = 0; k < nl; ++k)
+			{
+				const pcppx_layer& L = r->layers[(size_t)i * max_layers + k];
+				if (L.proto != 2)  // pcpp::IPv4: the first such layer
+					continue;
+				if (L.hdr_len >= 20 && L.hdr_len <= L.data_len && (uint32_t)L.offset + L.data_len <= cap)
+				{
+					groups[info[i].ip_key].push_back({ i, info[i].frag_offset, (uint32_t)(L.data_len - L.hdr_len), L.offset,
+					                                   L.hdr_len, (st & PCPPX_IPR_F_LAST) != 0 });
+					++candidates;
+				}
+				break;
+			}
+		}
+		for (int k = 0; k < PCPPX_DEFRAG_TOTALS; ++k)
+			o->totals[k] = 0;
+		o->totals[PCPPX_DEFRAG_CANDIDATES] = candidates;
+		o->totals[PCPPX_DEFRAG_BAD_DESC_N] = bad;
+		if (candidates > (s->max_fragments == 0 ? n : s->max_fragments))  // no room to form the groups
+		{
+			o->totals[PCPPX_DEFRAG_OVERFLOW] = 1;
+			return PCPPX_OK;
+		}
+		// the clean groups: members sorted by (frag_offset, source index), keyed by the completing member
+		struct Packet
+		{
+			std::vector<Frag> members;
+			uint32_t total;
+		};
+		std::map<uint32_t, Packet> done;
+		uint64_t merged = 0;
+		for (auto& kv : groups)
+		{
+			std::vector<Frag>& m = kv.second;
+			if (m.size() < 2 || m.size() > PCPPX_DEFRAG_MAX_FRAGS)
+				continue;
+			std::sort(m.begin(), m.end(),
+			          [](const Frag& x, const Frag& y) { return x.foff != y.foff ? x.foff < y.foff : x.idx < y.idx; });
+			uint32_t total = 0;
+			bool clean = true;
+			for (size_t k = 0; k < m.size() && clean; ++k)
+			{
+				clean = m[k].len > 0 && m[k].foff == total && m[k].last == (k + 1 == m.size());
+				total += m[k].len;
+			}
+			if (!clean || m[0].ip_off + m[0].hdr + total > PCPPX_MAX_CAPLEN || m[0].hdr + total > 65535)
+				continue;
+			uint32_t at = 0;
+			for (const Frag& f : m)
+			{
+				disp[f.idx] = PCPPX_DEFRAG_MERGED;
+				at = std::max(at, f.idx);
+			}
+			disp[at] = PCPPX_DEFRAG_MERGED_LAST;
+			merged += m.size();
+			done[at] = Packet{ m, total };
+		}
+		// the output's size, then (all or nothing) the output itself, in source order
+		uint64_t out_packets = 0, out_bytes = 0, left = 0;
+		for (uint32_t i = 0; i < n; ++i)
+		{
+			left += disp[i] == PCPPX_DEFRAG_LEFT;
+			if (disp[i] == PCPPX_DEFRAG_MERGED_LAST)
+			{
+				const Packet& p = done[i];
+				++out_packets;
+				out_bytes += p.members[0].ip_off + p.members[0].hdr + p.total;
+			}
+			else if (s->passthrough && (disp[i] == PCPPX_DEFRAG_PASS || disp[i] == PCPPX_DEFRAG_LEFT))
+			{
+				++out_packets;
+				out_bytes += b->caplens[i];
+			}
+		}
+		const bool overflow = out_packets > o->max_packets || (o->data != nullptr && out_bytes > o->data_cap);
+		o->totals[PCPPX_DEFRAG_OUT_PACKETS] = out_packets;
+		o->totals[PCPPX_DEFRAG_OUT_BYTES] = out_bytes;
+		o->totals[PCPPX_DEFRAG_REASSEMBLED] = done.size();
+		o->totals[PCPPX_DEFRAG_MERGED_FRAGS] = merged;
+		o->totals[PCPPX_DEFRAG_LEFT_FRAGS] = left;
+		o->totals[PCPPX_DEFRAG_OVERFLOW] = overflow ? 1 : 0;
+		if (overflow)
+			return PCPPX_OK;
+		uint32_t j = 0;
+		uint64_t pos = 0;
+		for (uint32_t i = 0; i < n; ++i)
+		{
+			if (o->disposition != nullptr)
+				o->disposition[i] = disp[i];
+			uint32_t len, first = i;
+			uint8_t frags = 0;
+			if (disp[i] == PCPPX_DEFRAG_MERGED_LAST)
+			{
+				const Packet& p = done[i];
+				const Frag& f = p.members[0];
+				len = f.ip_off + f.hdr + p.total;
+				first = f.idx;
+				frags = (uint8_t)p.members.size();
+				if (o->data != nullptr)
+				{
+					uint8_t* d = o->data + pos;
+					std::memcpy(d, b->data + b->offsets[f.idx], f.ip_off + f.hdr + f.len);
+					for (size_t k = 1; k < p.members.size(); ++k)
+					{
+						const Frag& x = p.members[k];
+						std::memcpy(d + f.ip_off + f.hdr + x.foff, b->data + b->offsets[x.idx] + x.ip_off + x.hdr, x.len);
+					}
+					// the header as computeCalculateFields leaves it: total length, no fragment word, the checksum
+					uint8_t* ip = d + f.ip_off;
+					const uint32_t tot_len = f.hdr + p.total;
+					ip[2] = (uint8_t)(tot_len >> 8);
+					ip[3] = (uint8_t)tot_len;
+					ip[6] = ip[7] = ip[10] = ip[11] = 0;
+					uint32_t sum = 0;
+					for (uint32_t k = 0; k < f.hdr; k += 2)
+						sum += ((uint32_t)ip[k] << 8) | (k + 1 < f.hdr ? ip[k + 1] : 0u);
+					while (sum >> 16)
+						sum = (sum & 0xFFFFu) + (sum >> 16);
+					ip[10] = (uint8_t)(~sum >> 8);
+					ip[11] = (uint8_t)~sum;
+				}
+			}
+			else if (s->passthrough && (disp[i] == PCPPX_DEFRAG_PASS || disp[i] == PCPPX_DEFRAG_LEFT))
+			{
+				len = b->caplens[i];
+				if (o->data != nullptr && len != 0)
+					std::memcpy(o->data + pos, b->data + b->offsets[i], len);
+			}
+			else
+				continue;
+			o->offsets[j] = pos;
+			o->caplens[j] = len;
+			if (o->index != nullptr)
+				o->index[j] = i;
+			if (o->first != nullptr)
+				o->first[j] = first;
+			if (o->frags != nullptr)
+				o->frags[j] = frags;
+			++j;
+			pos += len;
 		}
 		return PCPPX_OK;
 	}

@@ -55,6 +55,21 @@ uint32_t steer_blocks(uint32_t n);
 uint64_t steer_scratch_bytes(uint32_t n, uint32_t n_buckets);
 int launch_steer(const pcppx_batch* b, const pcppx_steer_spec* spec, const pcppx_steering* out, void* scratch,
                  hipStream_t stream);
+// pcppx_defrag_device (pcppx_defrag.hip): one clear and five to seven launches on `stream` (collect, verdict, count,
+// bases, place; with out->data the merge copy and the header patch). scratch: defrag_scratch_bytes(n, max_fragments)
+// bytes (include/pcppx.h gives the formula); one block takes kDefragBlockPk packets, the verdict / merge / patch
+// kernels kDefragCandPerBlock candidates; n_layers: packet 0's n_layers byte (a summary's or a brief's), nl_stride
+// bytes apart. Arguments are checked by the caller; n > 0.
+constexpr uint32_t kDefragBlockPk = 1024;
+constexpr uint32_t kDefragCandPerBlock = 256;
+constexpr uint32_t kDefragMinSlots = 64;
+uint32_t defrag_blocks(uint32_t n);
+uint32_t defrag_room(uint32_t n, uint32_t max_fragments);  // F: the candidates the scratch holds
+uint32_t defrag_slots(uint32_t room);                      // C: the group table's slots
+uint64_t defrag_scratch_bytes(uint32_t n, uint32_t max_fragments);
+int launch_defrag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
+                  uint32_t nl_stride, const pcppx_reasm_info* info, const pcppx_defrag_spec* spec,
+                  const pcppx_defragged* out, void* scratch, hipStream_t stream);
 // pcppx_bpf_device (pcppx_bpf.hip): one launch on `stream` (the caller has cleared out->totals on it). insns: the
 // validated programs back to back in device memory; program p is insns[start[p] .. start[p + 1]); uses_mem: bit p set
 // when program p loads from M[] (only then are its slots cleared). Arguments are checked by the caller; n > 0.

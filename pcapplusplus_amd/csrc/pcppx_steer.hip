@@ -217,56 +217,6 @@ __global__ __launch_bounds__(64) void steer_bases_kernel(uint32_t g, uint32_t K,
 	}
 }
 
-// the packet (lane number) that owns whole chunk c of the tile's flattened list: the last k <= 63 with cp[k] <= c (cp:
-// the exclusive prefix of the packets' whole-chunk counts, ascending; c < cp[64]). Packets without a whole chunk ahead
-// of it are passed over; branch-free.
-__device__ __forceinline__ uint32_t find_packet(const uint64_t* cp, uint64_t c)
-{
-	uint32_t k = 0;
-#pragma unroll
-	for (uint32_t step = 32; step != 0; step >>= 1)
-		k = cp[k + step] <= c ? k + step : k;
-	return k;
-}
-
-// the n (< 16) bytes at source position s (s % 16 = address % 16 from sbase) to destination position q: a packet's own
-// head or tail, [q, q + n) inside one aligned 16-B chunk. The one or two aligned granules that hold them are read;
-// n == 0 reads nothing. Stored in naturally aligned pieces of 1, 2, 4 and 8 B: sizes up to the widest boundary the
-// span reaches, then down again -- at most 6 stores, exactly the bytes owned.
-__device__ __forceinline__ void copy_edge(const uint8_t* sbase, uint8_t* dbase, uint64_t s, uint64_t q, uint32_t n)
-{
-	if (n == 0)
-		return;
-	const uint32_t so = (uint32_t)(s & 15);
-	const uint4* g = reinterpret_cast<const uint4*>(sbase + (s & ~15ull));
-	const uint4 ga = g[0];
-	const uint4 gb = g[so + n > 16 ? 1 : 0];
-	const uint4 r = funnel16(ga, gb, so);  // the span's bytes from byte 0
-	const uint4 zero = make_uint4(0, 0, 0, 0);
-	uint64_t cur = q;
-	const uint64_t e = q + n;
-	auto put = [&](uint32_t sz) {  // the sz bytes at cur
-		const uint4 x = funnel16(r, zero, (uint32_t)(cur - q));
-		if (sz == 1)
-			dbase[cur] = (uint8_t)x.x;
-		else if (sz == 2)
-			*reinterpret_cast<uint16_t*>(dbase + cur) = (uint16_t)x.x;
-		else if (sz == 4)
-			*reinterpret_cast<uint32_t*>(dbase + cur) = x.x;
-		else
-			*reinterpret_cast<uint2*>(dbase + cur) = make_uint2(x.x, x.y);
-		cur += sz;
-	};
-#pragma unroll
-	for (uint32_t sz = 1; sz <= 8; sz <<= 1)  // up: cur becomes a multiple of 2 * sz, or too little is left for sz
-		if ((cur & sz) != 0 && cur + sz <= e)
-			put(sz);
-#pragma unroll
-	for (uint32_t sz = 8; sz != 0; sz >>= 1)  // down: cur is a multiple of every size that still fits
-		if (cur + sz <= e)
-			put(sz);
-}
-
 __global__ __launch_bounds__(kStThreads) void steer_copy_kernel(StIn p, StOut o, uint32_t g,
                                                                 const uint32_t* __restrict__ cnt,
                                                                 const uint64_t* __restrict__ bytes)

@@ -186,6 +186,28 @@ class Engine:
         abi.check(self.lib.pcppx_steer_device(self.ctx, C.byref(b), C.byref(spec), C.byref(out),
                                               C.c_void_p(stream or 0)), "pcppx_steer_device")
 
+    def defrag_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, info,
+                      spec: abi.DefragSpec, out_offsets, out_caplens, totals, max_packets: int, out_data=None,
+                      data_cap: int = 0, out_index=None, out_first=None, out_frags=None, disposition=None,
+                      stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_defrag_device over device tensors: the IPv4 fragment groups that are complete and well formed
+        inside the batch are reassembled; with spec.passthrough every other packet is copied in place. summary (n * 32
+        bytes) or brief (n * 16 bytes): the parse's records, one of them; layers: FIXED, n * max_layers
+        * 8 bytes; info: n * 16 bytes (abi.REASM_DTYPE). out_data (u8, data_cap bytes; None = index-only), out_offsets
+        (i64) / out_caplens (i32) / out_index / out_first (i32) / out_frags (u8) of max_packets entries, disposition
+        (u8[n]), each of the last four optional; totals: 8 x i64 (abi.DEFRAG_*), overwritten. All or nothing: on
+        overflow only the totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.Defragged(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+                            opt(out_first), opt(out_frags), opt(disposition), max_packets, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_defrag_device(self.ctx, C.byref(b), C.byref(rec), max_layers, abi.ptr(info),
+                                               C.byref(spec), C.byref(out), C.c_void_p(stream or 0)),
+                  "pcppx_defrag_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -537,6 +559,64 @@ def steer_on_device(eng: Engine, batch: PacketBatch, bucket=None, key=None, key_
     if batch.frame_lens is not None:
         out.frame_lens = batch.frame_lens[index]
     return out, index, first.cpu().numpy().view(np.uint32), pos.cpu().numpy().view(np.uint64), tot
+
+
+def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, passthrough: bool = True,
+                     max_fragments: int = 0, data_cap: int | None = None, max_packets: int | None = None,
+                     index_only: bool = False, device: str = "cuda:0"):
+    """Copy a host batch and its parse to HBM, reassemble there the IPv4 fragment groups that are complete inside the
+    batch (pcppx_defrag_device), copy the result back: (PacketBatch of the output packets in source order; index u32 =
+    their source packet numbers, a reassembled packet's being the completing fragment's; first u32 = the packet whose
+    headers and timestamp each carries; frags u8 = fragments merged, 0 for a copied packet; disposition u8[n] =
+    abi.DEFRAG_* per source packet; totals dict).
+    records: the batch's summary or brief record array; layers: its FIXED [n, max_layers] layer array; info: its
+    abi.REASM_DTYPE array (Engine.parse_reasm_device gives all three in one pass). passthrough: copy every packet that
+    is not merged (IPDefragUtil's output), else only the reassembled packets come out. data_cap / max_packets default
+    to the batch's bytes / packets and max_fragments to n (always enough). All or nothing: when totals["overflow"] is
+    set the returned batch and columns are empty. timestamps_ns follow the packets through first, frame_lens through
+    index (a reassembled packet's frame length is its own length)."""
+    import torch
+
+    n = batch.n
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize not in (abi.BRIEF_DTYPE.itemsize, abi.SUMMARY_DTYPE.itemsize):
+        raise ValueError("records must be a summary or a brief record array")
+    lay = np.ascontiguousarray(layers)
+    ml = lay.shape[1]
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(device)  # noqa: E731
+    pad = lambda a: a if len(a) else np.zeros(1, a.dtype)  # noqa: E731
+    data, offsets, caplens = to_device(batch, device)
+    rec_t, lay_t, info_t = up(pad(rec)), up(pad(lay.reshape(-1))), up(pad(np.ascontiguousarray(info)))
+    cap = int(batch.caplens.sum(dtype=np.uint64)) if data_cap is None else data_cap
+    mp = n if max_packets is None else max_packets
+    out_data = None if index_only else torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    out_off = torch.empty(max(mp, 1), dtype=torch.int64, device=device)
+    out_cap = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_idx = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_first = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_frags = torch.empty(max(mp, 1), dtype=torch.uint8, device=device)
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    totals = torch.empty(abi.DEFRAG_TOTALS, dtype=torch.int64, device=device)
+    is_brief = rec.dtype.itemsize == abi.BRIEF_DTYPE.itemsize
+    eng.defrag_device(data, offsets, caplens, n, batch.linktype, lay_t, ml, info_t,
+                      abi.make_defrag_spec(passthrough, max_fragments), out_off, out_cap, totals, mp, out_data, cap,
+                      out_idx, out_first, out_frags, disp, torch.cuda.current_stream(device).cuda_stream,
+                      summary=None if is_brief else rec_t, brief=rec_t if is_brief else None)
+    torch.cuda.synchronize(device)
+    tot = abi.defrag_totals_dict(totals.cpu().numpy().view(np.uint64))
+    w, wb = (0, 0) if tot["overflow"] else (tot["out_packets"], tot["out_bytes"])
+    index = out_idx[:w].cpu().numpy().view(np.uint32)
+    first = out_first[:w].cpu().numpy().view(np.uint32)
+    frags = out_frags[:w].cpu().numpy()
+    out = PacketBatch(np.zeros(0, np.uint8) if index_only else out_data[:wb].cpu().numpy(),
+                      out_off[:w].cpu().numpy().view(np.uint64), out_cap[:w].cpu().numpy().view(np.uint32),
+                      batch.linktype)
+    if batch.timestamps_ns is not None:
+        out.timestamps_ns = batch.timestamps_ns[first]
+    if batch.frame_lens is not None:
+        out.frame_lens = np.where(frags != 0, out.caplens, batch.frame_lens[index]).astype(np.uint32)
+    dispo = np.zeros(0, np.uint8) if tot["overflow"] else disp[:n].cpu().numpy()
+    return out, index, first, frags, dispo, tot
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):

@@ -1,0 +1,138 @@
+"""A numpy IPv4 fragmenter: what Examples/IPFragUtil does to a capture, for a PacketBatch.
+
+fragment() splits the chosen IPv4 packets of a batch into fragments whose IP payload is at most frag_size bytes
+(rounded down to a multiple of 8), following splitIPPacketToFragmentsBySize (Examples/IPFragUtil/main.cpp:153-238):
+a packet whose IP payload is not larger than the fragment size is copied as it is; otherwise fragment j carries the
+packet's bytes up to the end of its IPv4 header (a trailer behind the IP payload is dropped), then payload bytes
+[j * size, min((j + 1) * size, payload)), with the total length, the fragment offset, MF on all but the last fragment
+(DF cleared: setIPv4FragmentParams overwrites the word) and the header checksum rewritten. The fragments of a packet
+take its place in the batch, in offset order. It is the input side of pcppx_defrag_device's tests and benchmark, and
+it is vectorised: no Python loop runs per packet.
+
+The IPv4 header is found behind Ethernet and up to two VLAN tags (the first IPv4 layer of such a packet); other
+packets, packets cut short of their IP payload's header, and packets that already are fragments are copied.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import abi
+from .pcap import PacketBatch
+
+_CHUNK = 1 << 25  # bytes gathered per step
+
+
+def locate_ipv4(batch: PacketBatch):
+    """(is_v4, ip_off, hdr, payload) per packet: the IPv4 header behind Ethernet and up to two VLAN tags, its length and
+    the IP payload's length (the total length field bounds it, and so does the capture). is_v4 is False where there is
+    none, where the header is cut short or malformed, or where the link type is not Ethernet."""
+    n = batch.n
+    off = batch.offsets.astype(np.int64)
+    cap = batch.caplens.astype(np.int64)
+    zero = np.zeros(n, np.int64)
+    if n == 0 or batch.linktype != abi.LINKTYPE_ETHERNET:
+        return np.zeros(n, bool), zero, zero.copy(), zero.copy()
+    d = batch.data
+    last = max(len(d) - 1, 0)
+
+    def u8(pos):
+        return d[np.minimum(off + pos, last)].astype(np.int64)
+
+    def be16(pos):
+        return (u8(pos) << 8) | u8(pos + 1)
+
+    ip_off = np.full(n, 14, np.int64)
+    et = be16(12)
+    for _ in range(2):
+        tagged = (et == 0x8100) | (et == 0x88A8)
+        et = np.where(tagged, be16(ip_off + 2), et)
+        ip_off = np.where(tagged, ip_off + 4, ip_off)
+    vihl = u8(ip_off)
+    hdr = (vihl & 15) * 4
+    total = be16(ip_off + 2)
+    ok = (et == 0x0800) & (cap >= ip_off + 20) & ((vihl >> 4) == 4) & (hdr >= 20) & (cap >= ip_off + hdr)
+    ok &= total >= hdr
+    avail = cap - ip_off
+    payload = np.where(ok, np.minimum(total, avail) - hdr, 0)
+    return ok, np.where(ok, ip_off, 0), np.where(ok, hdr, 0), payload
+
+
+def _gather(data: np.ndarray, starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
+    """The bytes of the ranges [starts[k], starts[k] + lens[k]) back to back."""
+    ends = np.cumsum(lens)
+    out = np.empty(int(ends[-1]) if len(ends) else 0, np.uint8)
+    k0 = 0
+    while k0 < len(lens):
+        base = int(ends[k0 - 1]) if k0 else 0
+        k1 = max(int(np.searchsorted(ends, base + _CHUNK, side="right")), k0 + 1)
+        ln = lens[k0:k1]
+        pos = ends[k0:k1] - ln - base  # where each range starts in this step's bytes
+        idx = np.repeat(starts[k0:k1] - pos, ln) + np.arange(int(ends[k1 - 1]) - base, dtype=np.int64)
+        out[base:int(ends[k1 - 1])] = data[idx]
+        k0 = k1
+    return out
+
+
+def fragment(batch: PacketBatch, frag_size: int, select=None) -> PacketBatch:
+    """The batch with its IPv4 packets split into fragments of at most frag_size payload bytes (a multiple of 8 after
+    rounding down; at least 8). select: a boolean mask of the packets to consider (None: all). meta["frag_src"]: the
+    source packet of every output packet; meta["frag_no"]: its fragment number (0 for a copied packet);
+    meta["frag_count"]: the fragments its source packet was split into (1: copied). timestamps_ns follow the source
+    packet; a fragment's frame length is its own length."""
+    fs = frag_size // 8 * 8
+    if fs < 8:
+        raise ValueError("frag_size must be at least 8")
+    n = batch.n
+    is_v4, ip_off, hdr, pay = locate_ipv4(batch)
+    off = batch.offsets.astype(np.int64)
+    cap = batch.caplens.astype(np.int64)
+    frag_word = np.zeros(n, np.int64)
+    if n:
+        d, last = batch.data, max(len(batch.data) - 1, 0)
+        at = np.minimum(off + ip_off + 6, last)
+        frag_word = np.where(is_v4, (d[at].astype(np.int64) << 8) | d[np.minimum(at + 1, last)], 0)
+    split = is_v4 & ((frag_word & 0x3FFF) == 0) & (pay > fs)
+    if select is not None:
+        split &= np.asarray(select, bool)
+    count = np.where(split, -(-pay // fs), 1)
+    src = np.repeat(np.arange(n, dtype=np.int64), count)
+    m = len(src)
+    no = np.arange(m, dtype=np.int64) - np.repeat(np.cumsum(count) - count, count)
+    is_frag = split[src]
+    head = np.where(is_frag, ip_off[src] + hdr[src], cap[src])  # the packet's own bytes, or a fragment's headers
+    piece = np.where(is_frag, np.minimum(fs, pay[src] - no * fs), 0)
+    starts = np.empty(2 * m, np.int64)
+    lens = np.empty(2 * m, np.int64)
+    starts[0::2], lens[0::2] = off[src], head
+    starts[1::2], lens[1::2] = off[src] + head + no * fs, piece
+    out_len = head + piece
+    out_off = np.cumsum(out_len) - out_len
+    data = _gather(batch.data, starts, lens)
+    # the fragments' IPv4 headers: total length, fragment word, checksum
+    f = np.nonzero(is_frag)[0]
+    if len(f):
+        ip = out_off[f] + ip_off[src[f]]
+        h = hdr[src[f]]
+        tot = h + piece[f]
+        word = (no[f] * fs // 8) | np.where(no[f] + 1 < count[src[f]], 0x2000, 0)
+        data[ip + 2], data[ip + 3] = (tot >> 8).astype(np.uint8), (tot & 255).astype(np.uint8)
+        data[ip + 6], data[ip + 7] = (word >> 8).astype(np.uint8), (word & 255).astype(np.uint8)
+        data[ip + 10] = data[ip + 11] = 0
+        cols = np.arange(60, dtype=np.int64)
+        rows = data[np.minimum(ip[:, None] + cols, len(data) - 1)].astype(np.int64)
+        rows[cols[None, :] >= h[:, None]] = 0
+        s = (rows[:, 0::2] << 8).sum(axis=1) + rows[:, 1::2].sum(axis=1)
+        s = (s & 0xFFFF) + (s >> 16)
+        s = (s & 0xFFFF) + (s >> 16)
+        ck = ~s & 0xFFFF
+        data[ip + 10], data[ip + 11] = (ck >> 8).astype(np.uint8), (ck & 255).astype(np.uint8)
+    out = PacketBatch(np.concatenate([data, np.zeros(1, np.uint8)]), out_off.astype(np.uint64),
+                      out_len.astype(np.uint32), batch.linktype)
+    if batch.timestamps_ns is not None:
+        out.timestamps_ns = batch.timestamps_ns[src]
+    if batch.frame_lens is not None:
+        out.frame_lens = np.where(is_frag, out_len, batch.frame_lens[src]).astype(np.uint32)
+    out.meta["frag_src"] = src.astype(np.uint32)
+    out.meta["frag_no"] = no.astype(np.uint32)
+    out.meta["frag_count"] = count[src].astype(np.uint32)
+    return out
