@@ -652,6 +652,131 @@ PCPPX_API int pcppx_defrag_device(pcppx_ctx* ctx, const pcppx_batch* batch, cons
 PCPPX_API int pcppx_defrag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                      const pcppx_reasm_info* info, const pcppx_defrag_spec* spec, pcppx_defragged* out);
 
+/* ---- frag: split the IPv4 packets of a device batch into fragments (IPFragUtil) ----
+ * The inverse of defrag, for packets that sit in HBM: what Examples/IPFragUtil does with
+ * splitIPPacketToFragmentsBySize (Examples/IPFragUtil/main.cpp:153-238). Every chosen IPv4 packet whose IP payload is
+ * larger than the fragment size is replaced, in place in the batch's order, by its fragments; the output is an ordinary
+ * pcppx_batch (parse it, send it on, or hand it to pcppx_defrag_device, which gives the packets back). One source
+ * packet produces up to 8,190 output packets. Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * Inputs: a device batch and its records from a device parse (FIXED layout, max_layers >= 1, the same max_layers here;
+ * the summary or, when it is NULL, the brief supplies n_layers; PACKED and DENSE records are refused), as in defrag; no
+ * pcppx_reasm_info is needed.
+ *
+ * The IPv4 layer of packet i: the first layer of protocol IPv4 among the first min(n_layers, max_layers) recorded
+ * entries, the one getLayerOfType<IPv4Layer>() returns (main.cpp:168-172). ip_off = layer.offset, hdr = layer.hdr_len,
+ * pay = layer.data_len - layer.hdr_len (getLayerPayloadSize(): a trailer behind the IP payload is excluded, a capture
+ * cut short bounds it). The layer must lie inside the packet and describe a header: 20 <= hdr <= 60, hdr <= data_len,
+ * offset + data_len <= caplen (always so for the records of a parse of this batch; records that say otherwise are
+ * never followed outside the packet: the packet is NOT_V4). Every encapsulation the parse handles is covered, since
+ * the layer comes from the records: VLAN, MPLS, SLL / SLL2, raw IP, GRE (the outer header) and so on.
+ *
+ * The fragment size fs of packet i: spec->frag_size (IPFragUtil's -s) in size mode; in mtu mode
+ * fs = (mtu - hdr) & ~7 (>= 8, since mtu >= 68 and hdr <= 60).
+ *
+ * Disposition of source packet i, the first rule that applies:
+ *   1 BAD_DESC    offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (the rule of select, steer and defrag):
+ *                 never read, never emitted
+ *   2 UNSELECTED  spec->keep != NULL and keep[i] == 0
+ *   3 NOT_V4      no IPv4 layer as defined above is recorded (non-IP and IPv6 packets, chains that stopped early)
+ *   4 ALREADY     be16(bytes 6-7 of the IP header) & 0x3FFF != 0: the packet is itself a fragment
+ *   5 FITS        size mode: pay <= fs (main.cpp:175); mtu mode: hdr + pay <= mtu
+ *   6 DF          spec->honor_df and bit 0x4000 of that word is set
+ *   7 SPLIT       everything else (pay > fs in both modes: at least two fragments)
+ * Two deliberate departures from the reference, which stay with the host: it re-fragments a packet that already is a
+ * fragment with offsets restarting at 0 (which corrupts the datagram; here ALREADY packets are copied), and it
+ * fragments IPv6 packets with a random fragment id (here IPv6 packets are NOT_V4). Without honor_df the reference's
+ * behaviour holds: DF is ignored and cleared.
+ *
+ * Fragments of a SPLIT packet (main.cpp:105-119, 185-237; IPv4Layer.cpp:372-413): c = ceil(pay / fs) of them,
+ * 2 <= c <= 8190. Fragment j (0 <= j < c) is bytes [0, ip_off + hdr) of the source followed by its payload bytes
+ * [j * fs, min((j + 1) * fs, pay)), `piece` bytes; in its IP header, bytes 2-3 = be16(hdr + piece), bytes
+ * 6-7 = be16((j * fs / 8) | (j < c - 1 ? 0x2000 : 0)) (all three flag bits of the source cleared, as the reference's
+ * & 0xff1f does) and bytes 10-11 = the RFC 1071 header checksum over the hdr bytes with that field zeroed (an odd last
+ * byte, which no real header has, padded with zero). Nothing else changes: the protocol byte stays, a trailer is
+ * dropped. Its caplen is ip_off + hdr + piece.
+ *
+ * Output, in source order: a SPLIT packet's fragments take its place, in offset order. With spec->copy_rest = 1 every
+ * other in-bounds packet (UNSELECTED, NOT_V4, ALREADY, FITS, DF) is copied unchanged in place: IPFragUtil with -a
+ * (copyAllPacketsToOutputFile). With copy_rest = 0 only the fragments come out: IPFragUtil without -a. The caller's
+ * -f / -d filters arrive as keep (pcppx_bpf_device's and pcppx_filter_device's matched[] are such columns). */
+typedef struct pcppx_frag_spec {
+	const uint8_t* keep; /* device, n bytes: packet i is considered iff keep[i] != 0. NULL = every packet */
+	uint32_t frag_size;  /* size mode: a multiple of 8 in 8..65528. Exactly one of frag_size and mtu is non-zero */
+	uint32_t mtu;        /* mtu mode: 68..65535 */
+	uint8_t copy_rest;   /* 0 / 1 */
+	uint8_t honor_df;    /* 0 / 1 */
+	uint8_t reserved[6];
+} pcppx_frag_spec;
+
+/* pcppx_fragmented.disposition values */
+#define PCPPX_FRAG_UNSELECTED 0
+#define PCPPX_FRAG_NOT_V4 1
+#define PCPPX_FRAG_ALREADY 2
+#define PCPPX_FRAG_FITS 3
+#define PCPPX_FRAG_DF 4
+#define PCPPX_FRAG_SPLIT 5
+#define PCPPX_FRAG_BAD_DESC 6
+
+/* pcppx_fragmented.totals words */
+#define PCPPX_FRAG_OUT_PACKETS 0   /* FRAGMENTS + COPIED */
+#define PCPPX_FRAG_OUT_BYTES 1
+#define PCPPX_FRAG_SPLIT_PACKETS 2 /* packets with disposition SPLIT */
+#define PCPPX_FRAG_FRAGMENTS 3     /* their fragments */
+#define PCPPX_FRAG_COPIED 4        /* packets copied unchanged (0 with copy_rest = 0) */
+#define PCPPX_FRAG_UNDER_SIZE 5    /* packets with disposition FITS (whatever copy_rest) */
+#define PCPPX_FRAG_BAD_DESC_N 6    /* packets with disposition BAD_DESC */
+#define PCPPX_FRAG_OVERFLOW 7
+#define PCPPX_FRAG_TOTALS 8
+
+typedef struct pcppx_fragmented { /* all device pointers (host pointers for pcppx_frag_reference) */
+	uint8_t* data;        /* packed bytes of the output packets, back to back, no padding; NULL = index-only */
+	uint64_t data_cap;
+	uint64_t* offsets;    /* max_packets entries */
+	uint32_t* caplens;    /* max_packets entries */
+	uint32_t* index;      /* optional (NULL): index[r] = source packet number of output packet r (non-decreasing) */
+	uint16_t* frag_no;    /* optional (NULL): frag_no[r] = j for fragment j; 0 for a copied packet */
+	uint16_t* counts;     /* optional (NULL): n entries: the output packets source packet i produced: 0, 1 or c */
+	uint8_t* disposition; /* optional (NULL): n entries, PCPPX_FRAG_* per source packet */
+	uint32_t max_packets;
+	uint32_t reserved;
+	uint64_t* totals;     /* PCPPX_FRAG_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_fragmented;
+
+/* Capacity is all or nothing, as in steer and defrag: OVERFLOW = 1 iff OUT_PACKETS > max_packets, or data != NULL and
+ * OUT_BYTES > data_cap. Then only the totals are written (no byte of data, no entry of offsets / caplens / index /
+ * frag_no / counts / disposition), and they hold the full would-be values. Sizing: make an index-only call first
+ * (data = NULL, max_packets = 0: it overflows and costs one pass over the records) and allocate OUT_PACKETS entries
+ * and OUT_BYTES bytes; or use a closed bound. With head_i = ip_off_i + hdr_i, a SPLIT packet puts out
+ * c_i * head_i + pay_i bytes, at most its caplen + (c_i - 1) * head_i, so
+ *   OUT_BYTES <= sum caplen_i + sum (c_i - 1) * head_i   and   OUT_PACKETS <= n + sum (c_i - 1),
+ * and from the descriptors alone, with F = frag_size (size mode) or (mtu - 60) & ~7 (mtu mode), c_i <= ceil(caplen_i / F),
+ * head_i + pay_i <= caplen_i and so (c_i - 1) * head_i < pay_i * head_i / F <= caplen_i^2 / (4 F):
+ *   OUT_PACKETS <= sum max(1, ceil(caplen_i / F))   and   OUT_BYTES <= sum (caplen_i + caplen_i^2 / (4 F)).
+ * With data == NULL no bytes move, the byte capacity is not applied and offsets hold the would-be positions.
+ * As the other movers: a packet of any caplen (0, or above PCPPX_MAX_CAPLEN) is copied; the source may be gapped,
+ * unordered or overlapping; out->data must not overlap batch->data. Source bytes are read only through aligned 16-B
+ * granules that hold a byte of a packet that is emitted, or as single bytes of the IPv4 header of an in-bounds,
+ * selected packet. Nothing outside [0, OUT_BYTES) of data or past the first OUT_PACKETS entries of offsets / caplens /
+ * index / frag_no is written, and nothing outside the n entries of counts / disposition. The output is a pure function
+ * of the inputs, bit-identical from run to run: every position comes from counts and scans, and there are no atomics.
+ * n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals, offsets or caplens; with n > 0 a
+ * null records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS; frag_size and mtu both zero or both set; a frag_size that is not a multiple of 8 in 8..65528; an
+ * mtu outside 68..65535; copy_rest or honor_df above 1; a non-zero reserved field. The work is queued on hip_stream
+ * and the call returns without waiting; calls on one context are ordered through its frag scratch (a buffer and an
+ * event of their own, as select's, steer's and defrag's). Scratch: with g = ceil(n / 1024) blocks, 52 g + 12 n bytes
+ * (per block its output packets and bytes and their exclusive prefixes, 64-bit each, and five 32-bit counts; per
+ * packet a 12-byte plan: the header's partial checksum, ip_off, pay, hdr and the disposition); PCPPX_E_NOMEM when it
+ * cannot be allocated. */
+PCPPX_API int pcppx_frag_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                uint8_t max_layers, const pcppx_frag_spec* spec, pcppx_fragmented* out,
+                                void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_frag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                   const pcppx_frag_spec* spec, pcppx_fragmented* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

@@ -256,6 +256,45 @@ def defrag_reference(batch: Batch, records: Records, max_layers: int, info, spec
                                                C.byref(out)), "pcppx_defrag_reference")
 
 
+# pcppx_frag_*: the IPv4 packets of a batch split into fragments (include/pcppx.h, frag)
+(FRAG_UNSELECTED, FRAG_NOT_V4, FRAG_ALREADY, FRAG_FITS, FRAG_DF, FRAG_SPLIT, FRAG_BAD_DESC) = range(7)  # disposition
+(FRAG_OUT_PACKETS, FRAG_OUT_BYTES, FRAG_SPLIT_PACKETS, FRAG_FRAGMENTS, FRAG_COPIED, FRAG_UNDER_SIZE, FRAG_BAD_DESC_N,
+ FRAG_OVERFLOW) = range(8)  # pcppx_fragmented.totals words
+FRAG_TOTALS = 8
+FRAG_FIELDS = ("out_packets", "out_bytes", "split_packets", "fragments", "copied", "under_size", "bad_desc", "overflow")
+
+
+class FragSpec(C.Structure):
+    """pcppx_frag_spec: the fragment size (or the MTU), the keep column, and what happens to the other packets."""
+    _fields_ = [("keep", C.c_void_p), ("frag_size", C.c_uint32), ("mtu", C.c_uint32), ("copy_rest", C.c_uint8),
+                ("honor_df", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+class Fragmented(C.Structure):
+    """pcppx_fragmented: the packed output batch, its per-packet columns, the per-source columns and the totals."""
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("offsets", C.c_void_p), ("caplens", C.c_void_p),
+                ("index", C.c_void_p), ("frag_no", C.c_void_p), ("counts", C.c_void_p), ("disposition", C.c_void_p),
+                ("max_packets", C.c_uint32), ("reserved", C.c_uint32), ("totals", C.c_void_p)]
+
+
+def make_frag_spec(frag_size: int = 0, mtu: int = 0, keep=None, copy_rest: bool = True,
+                   honor_df: bool = False) -> FragSpec:
+    """frag_size (IPFragUtil's -s: a multiple of 8 in 8..65528) or mtu (68..65535), exactly one of them; keep: the
+    address of the n-byte column of the packets to consider (None: all); copy_rest: IPFragUtil's -a."""
+    return FragSpec(keep, frag_size, mtu, 1 if copy_rest else 0, 1 if honor_df else 0)
+
+
+def frag_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(FRAG_FIELDS)}
+
+
+def frag_reference(batch: Batch, records: Records, max_layers: int, spec: FragSpec, out: Fragmented) -> None:
+    """pcppx_frag_reference: pcppx_frag_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_frag_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                             C.byref(out)), "pcppx_frag_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -468,6 +507,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_defrag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P, C.POINTER(DefragSpec),
                                            C.POINTER(Defragged)]
     lib.pcppx_defrag_reference.restype = C.c_int
+    lib.pcppx_frag_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(FragSpec),
+                                      C.POINTER(Fragmented), P]
+    lib.pcppx_frag_device.restype = C.c_int
+    lib.pcppx_frag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(FragSpec),
+                                         C.POINTER(Fragmented)]
+    lib.pcppx_frag_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -494,7 +539,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_pcap_read_batch", "pcppx_pcap_read_batch_ex", "pcppx_pcap_map_batch", "pcppx_pcap_close", "pcppx_host_alloc", "pcppx_host_free",
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
-    "pcppx_defrag_device", "pcppx_defrag_reference",
+    "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_frag_device", "pcppx_frag_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

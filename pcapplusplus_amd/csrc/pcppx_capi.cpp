@@ -242,6 +242,8 @@ struct pcppx_ctx
 	Scratch steer;
 	// pcppx_defrag_device: the group table, the candidate records and the block sums (defrag_scratch_bytes)
 	Scratch defrag;
+	// pcppx_frag_device: the block sums and bases and the per-packet plans (frag_scratch_bytes)
+	Scratch frag;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -918,6 +920,8 @@ extern "C"
 		c->steer.release(c->stream);
 		c->defrag.wait();
 		c->defrag.release(c->stream);
+		c->frag.wait();
+		c->frag.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -928,7 +932,7 @@ extern "C"
 			(void)hipFree(c->d_win);
 			(void)hipHostFree(c->h_win);
 		}
-		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag })
+		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->frag })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1681,6 +1685,193 @@ extern "C"
 				o->frags[j] = frags;
 			++j;
 			pos += len;
+		}
+		return PCPPX_OK;
+	}
+}
+
+// ---- frag: the IPv4 packets of a batch split into fragments (include/pcppx.h, frag) ----
+namespace
+{
+// the argument rules pcppx_frag_device and pcppx_frag_reference share (include/pcppx.h)
+bool valid_frag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag_spec* s,
+                const pcppx_fragmented* o)
+{
+	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
+	    o->caplens == nullptr)
+		return false;
+	if (max_layers == 0 || max_layers > PCPPX_MAX_LAYERS || r->layout != PCPPX_LAYOUT_FIXED)
+		return false;
+	if ((s->frag_size == 0) == (s->mtu == 0))
+		return false;
+	if (s->frag_size != 0 && (s->frag_size % 8 != 0 || s->frag_size > 65528))
+		return false;
+	if (s->mtu != 0 && (s->mtu < 68 || s->mtu > 65535))
+		return false;
+	if (s->copy_rest > 1 || s->honor_df > 1 || o->reserved != 0)
+		return false;
+	for (uint8_t x : s->reserved)
+		if (x != 0)
+			return false;
+	if (b->n != 0 && (r->layers == nullptr || (r->summary == nullptr && r->brief == nullptr)))
+		return false;
+	return valid_batch(b);
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_frag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                      const pcppx_frag_spec* s, pcppx_fragmented* o, void* hip_stream)
+	{
+		if (c == nullptr || !valid_frag(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_FRAG_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous frag (possibly queued on another stream) owns the plans until it is done
+		int rc = c->frag.acquire(st, pcppx::frag_scratch_bytes(b->n));
+		if (rc != PCPPX_OK)
+			return rc;
+		uint32_t stride;
+		const uint8_t* nl = n_layers_column(r, stride);
+		rc = pcppx::launch_frag(b, r->layers, max_layers, nl, stride, s, o, c->frag.ptr, st);
+		return rc != PCPPX_OK ? rc : c->frag.mark_used(st);
+	}
+
+	int pcppx_frag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag_spec* s,
+	                         pcppx_fragmented* o)
+	{
+		if (!valid_frag(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		const uint32_t n = b->n;
+		struct Src
+		{
+			uint8_t disp;
+			uint32_t ip_off, hdr, pay, fs, count;  // of a SPLIT packet
+		};
+		std::vector<Src> src(n);
+		uint32_t stride = 0;
+		const uint8_t* nlc = n != 0 ? n_layers_column(r, stride) : nullptr;
+		uint64_t out_packets = 0, out_bytes = 0, split = 0, fragments = 0, copied = 0, fits = 0, bad = 0;
+		for (uint32_t i = 0; i < n; ++i)
+		{
+			Src& x = src[i];
+			x = Src{ PCPPX_FRAG_BAD_DESC, 0, 0, 0, 0, 0 };
+			uint64_t off;
+			uint32_t cap;
+			if (out_of_bounds(b, 0, i, off, cap))
+			{
+				++bad;
+				continue;
+			}
+			x.disp = [&]() -> uint8_t {
+				if (s->keep != nullptr && s->keep[i] == 0)
+					return PCPPX_FRAG_UNSELECTED;
+				const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
+				const pcppx_layer* L = nullptr;
+				for (uint32_t k = 0; k < nl && L == nullptr; ++k)
+					if (r->layers[(size_t)i * max_layers + k].proto == 2)  // pcpp::IPv4: the first such layer
+						L = &r->layers[(size_t)i * max_layers + k];
+				if (L == nullptr || L->hdr_len < 20 || L->hdr_len > 60 || L->hdr_len > L->data_len ||
+				    (uint32_t)L->offset + L->data_len > cap)
+					return PCPPX_FRAG_NOT_V4;
+				x.ip_off = L->offset;
+				x.hdr = L->hdr_len;
+				x.pay = (uint32_t)L->data_len - L->hdr_len;
+				x.fs = s->frag_size != 0 ? s->frag_size : ((s->mtu - x.hdr) & ~7u);
+				const uint8_t* ip = b->data + off + x.ip_off;
+				const uint32_t word = ((uint32_t)ip[6] << 8) | ip[7];
+				if ((word & 0x3FFFu) != 0)
+					return PCPPX_FRAG_ALREADY;
+				if (s->frag_size != 0 ? x.pay <= x.fs : x.hdr + x.pay <= s->mtu)
+					return PCPPX_FRAG_FITS;
+				if (s->honor_df != 0 && (word & 0x4000u) != 0)
+					return PCPPX_FRAG_DF;
+				return PCPPX_FRAG_SPLIT;
+			}();
+			fits += x.disp == PCPPX_FRAG_FITS;
+			if (x.disp == PCPPX_FRAG_SPLIT)
+			{
+				x.count = (x.pay + x.fs - 1) / x.fs;
+				++split;
+				fragments += x.count;
+				out_bytes += (uint64_t)x.count * (x.ip_off + x.hdr) + x.pay;
+			}
+			else if (s->copy_rest != 0)
+			{
+				x.count = 1;
+				++copied;
+				out_bytes += cap;
+			}
+			out_packets += x.count;
+		}
+		const bool overflow = out_packets > o->max_packets || (o->data != nullptr && out_bytes > o->data_cap);
+		o->totals[PCPPX_FRAG_OUT_PACKETS] = out_packets;
+		o->totals[PCPPX_FRAG_OUT_BYTES] = out_bytes;
+		o->totals[PCPPX_FRAG_SPLIT_PACKETS] = split;
+		o->totals[PCPPX_FRAG_FRAGMENTS] = fragments;
+		o->totals[PCPPX_FRAG_COPIED] = copied;
+		o->totals[PCPPX_FRAG_UNDER_SIZE] = fits;
+		o->totals[PCPPX_FRAG_BAD_DESC_N] = bad;
+		o->totals[PCPPX_FRAG_OVERFLOW] = overflow ? 1 : 0;
+		if (overflow)
+			return PCPPX_OK;
+		uint32_t j = 0;
+		uint64_t pos = 0;
+		for (uint32_t i = 0; i < n; ++i)
+		{
+			const Src& x = src[i];
+			if (o->disposition != nullptr)
+				o->disposition[i] = x.disp;
+			if (o->counts != nullptr)
+				o->counts[i] = (uint16_t)x.count;
+			for (uint32_t f = 0; f < x.count; ++f)
+			{
+				const uint8_t* from = b->data + b->offsets[i];
+				uint32_t len = b->caplens[i];
+				if (x.disp != PCPPX_FRAG_SPLIT)
+				{
+					if (o->data != nullptr && len != 0)
+						std::memcpy(o->data + pos, from, len);
+				}
+				else
+				{
+					const uint32_t head = x.ip_off + x.hdr, piece = std::min(x.fs, x.pay - f * x.fs);
+					len = head + piece;
+					if (o->data != nullptr)
+					{
+						uint8_t* d = o->data + pos;
+						std::memcpy(d, from, head);
+						std::memcpy(d + head, from + head + (size_t)f * x.fs, piece);
+						// the header as setIPv4FragmentParams and computeCalculateFields leave it
+						uint8_t* ip = d + x.ip_off;
+						const uint32_t tot_len = x.hdr + piece, word = (f * x.fs / 8) | (f + 1 < x.count ? 0x2000u : 0u);
+						ip[2] = (uint8_t)(tot_len >> 8);
+						ip[3] = (uint8_t)tot_len;
+						ip[6] = (uint8_t)(word >> 8);
+						ip[7] = (uint8_t)word;
+						ip[10] = ip[11] = 0;
+						uint32_t sum = 0;
+						for (uint32_t k = 0; k < x.hdr; k += 2)
+							sum += ((uint32_t)ip[k] << 8) | (k + 1 < x.hdr ? ip[k + 1] : 0u);
+						while (sum >> 16)
+							sum = (sum & 0xFFFFu) + (sum >> 16);
+						ip[10] = (uint8_t)(~sum >> 8);
+						ip[11] = (uint8_t)~sum;
+					}
+				}
+				o->offsets[j] = pos;
+				o->caplens[j] = len;
+				if (o->index != nullptr)
+					o->index[j] = i;
+				if (o->frag_no != nullptr)
+					o->frag_no[j] = (uint16_t)f;
+				++j;
+				pos += len;
+			}
 		}
 		return PCPPX_OK;
 	}

@@ -70,6 +70,16 @@ uint64_t defrag_scratch_bytes(uint32_t n, uint32_t max_fragments);
 int launch_defrag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
                   uint32_t nl_stride, const pcppx_reasm_info* info, const pcppx_defrag_spec* spec,
                   const pcppx_defragged* out, void* scratch, hipStream_t stream);
+// pcppx_frag_device (pcppx_frag.hip): three or four launches on `stream` (plan, bases, emit; with out->data the header
+// patch). scratch: frag_scratch_bytes(n) bytes (include/pcppx.h gives the formula); one block takes kFragBlockPk source
+// packets and puts out all of their output packets; n_layers / nl_stride as for launch_defrag. Arguments are checked
+// by the caller; n > 0.
+constexpr uint32_t kFragBlockPk = 1024;
+uint32_t frag_blocks(uint32_t n);
+uint64_t frag_scratch_bytes(uint32_t n);
+int launch_frag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
+                uint32_t nl_stride, const pcppx_frag_spec* spec, const pcppx_fragmented* out, void* scratch,
+                hipStream_t stream);
 // pcppx_bpf_device (pcppx_bpf.hip): one launch on `stream` (the caller has cleared out->totals on it). insns: the
 // validated programs back to back in device memory; program p is insns[start[p] .. start[p + 1]); uses_mem: bit p set
 // when program p loads from M[] (only then are its slots cleared). Arguments are checked by the caller; n > 0.

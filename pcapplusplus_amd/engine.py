@@ -208,6 +208,27 @@ class Engine:
                                                C.byref(spec), C.byref(out), C.c_void_p(stream or 0)),
                   "pcppx_defrag_device")
 
+    def frag_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.FragSpec,
+                    out_offsets, out_caplens, totals, max_packets: int, out_data=None, data_cap: int = 0,
+                    out_index=None, out_frag_no=None, counts=None, disposition=None, stream: int | None = None,
+                    data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_frag_device over device tensors: the IPv4 packets spec chooses (abi.make_frag_spec) whose IP
+        payload exceeds the fragment size are split into fragments in place; with spec.copy_rest every other packet is
+        copied. summary (n * 32 bytes) or brief (n * 16 bytes): the parse's records, one of them; layers: FIXED,
+        n * max_layers * 8 bytes. out_data (u8, data_cap bytes; None = index-only), out_offsets (i64) / out_caplens
+        (i32) / out_index (i32) / out_frag_no (i16) of max_packets entries, counts (i16[n]), disposition (u8[n]), each
+        of the last four optional; totals: 8 x i64 (abi.FRAG_*), overwritten. All or nothing: on overflow only the
+        totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.Fragmented(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+                             opt(out_frag_no), opt(counts), opt(disposition), max_packets, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_frag_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_frag_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -617,6 +638,72 @@ def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, pas
         out.frame_lens = np.where(frags != 0, out.caplens, batch.frame_lens[index]).astype(np.uint32)
     dispo = np.zeros(0, np.uint8) if tot["overflow"] else disp[:n].cpu().numpy()
     return out, index, first, frags, dispo, tot
+
+
+def frag_on_device(eng: Engine, batch: PacketBatch, records, layers, frag_size: int = 0, mtu: int = 0, keep=None,
+                   copy_rest: bool = True, honor_df: bool = False, data_cap: int | None = None,
+                   max_packets: int | None = None, index_only: bool = False, device: str = "cuda:0"):
+    """Copy a host batch and its parse to HBM, split its IPv4 packets into fragments there (pcppx_frag_device), copy
+    the result back: (PacketBatch of the output packets in source order, a split packet's fragments in its place; index
+    u32 = their source packet numbers; frag_no u16 = the fragment's number, 0 for a copied packet; disposition u8[n] =
+    abi.FRAG_* per source packet; totals dict).
+    records: the batch's summary or brief record array; layers: its FIXED [n, max_layers] layer array. frag_size
+    (IPFragUtil's -s) or mtu, one of them; keep: a mask of the packets to consider (None: all; IPFragUtil's -f / -d
+    filters); copy_rest: copy every packet that is not split (IPFragUtil's -a), else only fragments come out. data_cap
+    / max_packets default to what an index-only call says the output needs. All or nothing: when totals["overflow"] is
+    set the returned batch and columns are empty. timestamps_ns follow the packets through index; a fragment's frame
+    length is its caplen, a copied packet keeps its own."""
+    import torch
+
+    n = batch.n
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize not in (abi.BRIEF_DTYPE.itemsize, abi.SUMMARY_DTYPE.itemsize):
+        raise ValueError("records must be a summary or a brief record array")
+    lay = np.ascontiguousarray(layers)
+    ml = lay.shape[1]
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(device)  # noqa: E731
+    pad = lambda a: a if len(a) else np.zeros(1, a.dtype)  # noqa: E731
+    data, offsets, caplens = to_device(batch, device)
+    rec_t, lay_t = up(pad(rec)), up(pad(lay.reshape(-1)))
+    keep_t = None if keep is None else up(pad(np.ascontiguousarray(keep).astype(np.uint8)))
+    spec = abi.make_frag_spec(frag_size, mtu, None if keep_t is None else abi.ptr(keep_t), copy_rest, honor_df)
+    is_brief = rec.dtype.itemsize == abi.BRIEF_DTYPE.itemsize
+    st = torch.cuda.current_stream(device).cuda_stream
+    totals = torch.empty(abi.FRAG_TOTALS, dtype=torch.int64, device=device)
+    one64, one32 = torch.empty(1, dtype=torch.int64, device=device), torch.empty(1, dtype=torch.int32, device=device)
+
+    def call(out_off, out_cap, mp, out_data=None, cap=0, idx=None, no=None, cnt=None, disp=None):
+        eng.frag_device(data, offsets, caplens, n, batch.linktype, lay_t, ml, spec, out_off, out_cap, totals, mp,
+                        out_data, cap, idx, no, cnt, disp, st, summary=None if is_brief else rec_t,
+                        brief=rec_t if is_brief else None)
+        torch.cuda.synchronize(device)
+        return abi.frag_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    if data_cap is None or max_packets is None:  # the sizing call: index-only, no room, so only the totals are written
+        need = call(one64, one32, 0)
+        data_cap = need["out_bytes"] if data_cap is None else data_cap
+        max_packets = need["out_packets"] if max_packets is None else max_packets
+    cap, mp = data_cap, max_packets
+    out_data = None if index_only else torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    out_off = torch.empty(max(mp, 1), dtype=torch.int64, device=device)
+    out_cap = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_idx = torch.empty(max(mp, 1), dtype=torch.int32, device=device)
+    out_no = torch.empty(max(mp, 1), dtype=torch.int16, device=device)
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(out_off, out_cap, mp, out_data, cap, out_idx, out_no, None, disp)
+    w, wb = (0, 0) if tot["overflow"] else (tot["out_packets"], tot["out_bytes"])
+    index = out_idx[:w].cpu().numpy().view(np.uint32)
+    frag_no = out_no[:w].cpu().numpy().view(np.uint16)
+    dispo = np.zeros(0, np.uint8) if tot["overflow"] else disp[:n].cpu().numpy()
+    out = PacketBatch(np.zeros(0, np.uint8) if index_only else out_data[:wb].cpu().numpy(),
+                      out_off[:w].cpu().numpy().view(np.uint64), out_cap[:w].cpu().numpy().view(np.uint32),
+                      batch.linktype)
+    if batch.timestamps_ns is not None:
+        out.timestamps_ns = batch.timestamps_ns[index]
+    if batch.frame_lens is not None:
+        split = dispo[index] == abi.FRAG_SPLIT if w else np.zeros(0, bool)
+        out.frame_lens = np.where(split, out.caplens, batch.frame_lens[index]).astype(np.uint32)
+    return out, index, frag_no, dispo, tot
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
