@@ -652,6 +652,154 @@ PCPPX_API int pcppx_defrag_device(pcppx_ctx* ctx, const pcppx_batch* batch, cons
 PCPPX_API int pcppx_defrag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                      const pcppx_reasm_info* info, const pcppx_defrag_spec* spec, pcppx_defragged* out);
 
+/* ---- tcpstream: reassemble the TCP connection sides that are clean inside one device batch (TcpReassembly) ----
+ * pcppx_reasm_device stops at the connection table; this is the table's common case, for packets that sit in HBM:
+ * what TcpReassembly::reassemblePacket (Packet++/src/TcpReassembly.cpp:81-486, line numbers below are that file's)
+ * delivers to its OnMessageReady callback. Connection sides that are clean inside the batch are reassembled on the
+ * device into contiguous stream bytes; every other packet is labelled and left for the caller's host TcpReassembly.
+ * Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * Inputs: as defrag. A device batch, its FIXED records (max_layers >= 1, the same max_layers here; the summary or, when
+ * it is NULL, the brief supplies hash5, n_layers and l4_layer; PACKED and DENSE records are refused) and info[n], an
+ * input column that is never recomputed: any info and any hash5 are legal.
+ *
+ * Candidates: packet i is a candidate iff (info[i].tcp_status & 15) == PCPPX_TCPR_DATA, its descriptor is in bounds (the
+ * shared rule, the 64-bit wrap checked), l4_layer < min(n_layers, max_layers) and that layer has protocol TCP (4), the
+ * TCP header's first 20 bytes and the payload [offset + hdr_len, offset + hdr_len + info[i].tcp_payload) lie inside
+ * caplen, and the chain records an IP layer: the first entry of protocol IPv4 (2) or IPv6 (3), which is
+ * getLayerOfType<IPLayer>() (:96-100), whose source address (4 bytes at IP + 12, or 16 bytes at IP + 8) lies inside
+ * caplen. From the bytes: seq = be32 at TCP + 4, the source port = the 2 raw bytes at TCP + 0 (:192), the source
+ * address. SYN / FIN / RST come from info[i].tcp_status and len from info[i].tcp_payload. Records that point outside
+ * the packet are never followed: such a packet is LEFT, as is every other DATA packet that is no candidate.
+ *
+ * Connections: all candidates with the same hash5; the 32-bit key alone decides, exactly as m_ConnectionList is keyed
+ * (:141-147). Key 0 is legal. Side 0 is the (address family, address, port) of the connection's candidate with the
+ * lowest source index, side 1 that of the lowest-index candidate that differs from side 0 (:195-225). A candidate that
+ * matches neither is LEFT (:239-245: it returns before it touches any state) and affects nothing else.
+ *
+ * Clean sides: in source order, the side's first member fixes start = seq + (SYN ? 1 : 0) (:312-319), and
+ * rel = (seq - start) mod 2^32. A side is reassembled iff
+ *   1. no member has SYN and len > 0 (:409-410 would skip a sequence number);
+ *   2. every data member (len > 0) has rel < 2^31, the side's total is < 2^31, and the data members sorted by rel tile
+ *      [0, total) exactly: no gap, overlap or duplicate (a retransmission or a keep-alive leaves the side to the host);
+ *   3. the side's lowest-index FIN-or-RST member has an index >= every data member of the side;
+ *   4. the connection's lowest-index RST member (of either side) has an index >= every data member of both sides;
+ *   5. with base_clear = 1: the side is in order (source order = rel order over its data members), or the other side
+ *      has no data member besides, at most, its own first member;
+ *   6. it has at least one data byte.
+ * A side is judged on its own: one side of a connection may be clean and the other not.
+ * For a clean side the callbacks deliver exactly each data member's whole payload, once, in rel order. `sequence`, the
+ * side's next expected number, is start plus the length of a tiling prefix at all times: the first member sets it
+ * (:317-319); a data member at `sequence` is delivered whole and advances it (:382-419), then checkOutOfOrderFragments
+ * (:558-583) releases, whole and in rel order, the parked members that now continue the prefix; a member above
+ * `sequence` is parked (:436-468, the list is unlimited with maxOutOfOrderFragments = 0); no member is ever below
+ * `sequence` (the tiling has no overlap), so neither trimming path (:340-379, :586-627) runs. Zero-length members move
+ * nothing (:385-400, :439-454; a zero-length SYN after the first is at most an ignored retransmission). What could
+ * flush the parked list as "[N bytes missing]" or ignore later data is ruled out: the other-side flush (:297-305)
+ * needs parked members of this side (not in order) while a data member of the other side arrives that is not that
+ * side's first member (condition 5; with base_clear = 0 the flush does not exist); handleFinOrRst (:501-527) flushes
+ * this side or closes the flow only on a FIN / RST of this side, which by condition 3 comes when every data member has
+ * arrived and, the tiling being complete, none is parked, or on a RST (:258-261, :525-526), which by condition 4 comes
+ * after all data of both sides; the flow is closed (:173-177) only by a RST or by the FIN of both sides, and this side
+ * ignores data (:256-268) only after its own FIN / RST. When the last data member (by index) has arrived the prefix is
+ * the whole tiling, so everything has been delivered.
+ * Where this rule is stricter than the text of the issue that asked for it, the code of the reference decided: a
+ * zero-length FIN / RST as a side's first member returns at :271-276 before `sequence` is set, and later data of that
+ * side is ignored (:256), which condition 3 already says.
+ *
+ * Output: data holds the stream bytes of the clean sides back to back, ordered by the source index of each side's
+ * first member; each stream is its data members' payloads in rel order. streams[j] describes stream j. The optional
+ * per-packet columns give every source packet's part. */
+typedef struct pcppx_tcpstream_spec {
+	uint32_t max_segments; /* the candidates the call has room for; 0 = n (always enough) */
+	uint8_t base_clear;    /* 0 / 1: TcpReassemblyConfiguration::enableBaseBufferClearCondition (the reference's default
+	                          is 1). maxOutOfOrderFragments is modelled at its default 0 (unlimited) */
+	uint8_t reserved[3];
+} pcppx_tcpstream_spec;
+
+/* pcppx_tcpstream_rec.flags */
+#define PCPPX_TCPS_F_SYN 0x01 /* some member of the side has SYN */
+#define PCPPX_TCPS_F_FIN 0x02
+#define PCPPX_TCPS_F_RST 0x04
+#define PCPPX_TCPS_F_OOO 0x08 /* the data members did not arrive in rel order */
+
+typedef struct pcppx_tcpstream_rec { /* 32 bytes per clean side */
+	uint64_t pos;      /* byte position of the stream in data */
+	uint32_t bytes;    /* its length (< 2^31) */
+	uint32_t flow_key; /* hash5 */
+	uint32_t first;    /* source index of the side's first member */
+	uint32_t segments; /* its data members */
+	uint32_t peer;     /* the record number of the connection's other side, or 0xFFFFFFFF when that is not clean */
+	uint8_t side;      /* 0 / 1 */
+	uint8_t flags;     /* PCPPX_TCPS_F_* */
+	uint8_t reserved[2];
+} pcppx_tcpstream_rec;
+
+/* pcppx_tcpstreams.disposition values */
+#define PCPPX_TCPS_NOT_TCP 0  /* status other than DATA and HOST (in bounds) */
+#define PCPPX_TCPS_HOST 1     /* status PCPPX_TCPR_HOST: the host decides, and it may belong to any connection */
+#define PCPPX_TCPS_LEFT 2     /* a DATA packet the device did not reassemble: what the host TcpReassembly is fed */
+#define PCPPX_TCPS_STREAM 3   /* a data member of a clean side: its payload is in data */
+#define PCPPX_TCPS_CONTROL 4  /* a zero-length member (SYN / FIN / RST) of a clean side */
+#define PCPPX_TCPS_BAD_DESC 5 /* the descriptor is out of bounds: never read */
+
+/* pcppx_tcpstreams.totals words */
+#define PCPPX_TCPS_STREAMS 0
+#define PCPPX_TCPS_BYTES 1
+#define PCPPX_TCPS_SEGMENTS 2   /* packets with disposition STREAM */
+#define PCPPX_TCPS_LEFT_N 3     /* packets with disposition LEFT */
+#define PCPPX_TCPS_CANDIDATES 4
+#define PCPPX_TCPS_HOST_N 5     /* packets with disposition HOST */
+#define PCPPX_TCPS_BAD_DESC_N 6 /* packets with disposition BAD_DESC */
+#define PCPPX_TCPS_OVERFLOW 7
+#define PCPPX_TCPS_TOTALS 8
+#define PCPPX_TCPS_NONE 0xFFFFFFFFu
+
+typedef struct pcppx_tcpstreams { /* all device pointers (host pointers for pcppx_tcpstream_reference) */
+	uint8_t* data;                /* the stream bytes, back to back, no padding; NULL = index-only */
+	uint64_t data_cap;
+	pcppx_tcpstream_rec* streams; /* max_streams entries */
+	uint8_t* disposition;         /* optional (NULL): n entries, PCPPX_TCPS_* per source packet */
+	uint32_t* seg_stream;         /* optional (NULL): n entries, the record number of a STREAM / CONTROL packet's side,
+	                                 else PCPPX_TCPS_NONE */
+	uint32_t* seg_pos;            /* optional (NULL): n entries, a STREAM / CONTROL packet's rel (a STREAM packet's payload
+	                                 is at streams[seg_stream].pos + seg_pos), else 0 */
+	uint32_t max_streams;
+	uint32_t reserved;
+	uint64_t* totals;             /* PCPPX_TCPS_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_tcpstreams;
+
+/* Capacity is all or nothing, as in steer and defrag: OVERFLOW = 1 iff STREAMS > max_streams, or data != NULL and
+ * BYTES > data_cap, or CANDIDATES > max_segments (0 = n). Then only the totals are written (no byte of data, no entry
+ * of streams or of the per-packet columns): they hold the full would-be values, except that with
+ * CANDIDATES > max_segments the connections cannot be formed and only CANDIDATES, HOST_N, BAD_DESC_N and OVERFLOW are
+ * given (the other words are 0), as in defrag. max_streams = n, data_cap = the sum of the caplens and max_segments = n
+ * always suffice. With data == NULL no bytes move, the byte capacity is not applied and pos holds the would-be positions.
+ * As the other movers: the source may be gapped, unordered or overlapping; out->data must not overlap batch->data. Source
+ * bytes are read only through aligned 16-B granules that hold a byte of an emitted payload, or as single header bytes of
+ * an in-bounds candidate. Nothing outside [0, BYTES) of data, past the first STREAMS entries of streams or the n entries
+ * of the per-packet columns is written. The output is a pure function of the inputs, bit-identical from run to run:
+ * positions come from counts, scans and rel; atomics only form sets, sums, minima and maxima. n == 0 is legal (zero
+ * totals). PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals or streams; with n > 0 a
+ * null info, records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS; base_clear above 1; a non-zero reserved field. The work is queued on hip_stream and the call returns
+ * without waiting; calls on one context are ordered through its tcpstream scratch (a buffer and an event of their own).
+ * Scratch: with g = ceil(n / 1024) blocks, F = min(max_segments or n, n) and C = the power of two >= max(2F, 64):
+ * 16 + 40 g + 4 n + 64 F + 120 C bytes (block sums and bases, one word per packet, one record per candidate, one
+ * connection slot with its two sides and one segment slot per table entry; the tables are cleared by every call);
+ * PCPPX_E_NOMEM when it cannot be allocated.
+ * The call is batch-local. A caller that keeps a host TcpReassembly across batches must know that its table holds
+ * nothing for a key before trusting a stream of that key; the LEFT packets are what it feeds that table. HOST packets
+ * may belong to any connection: with a non-zero HOST_N the result is conditional on what the host finds in them.
+ * "[N bytes missing]" markers, retransmission trimming and timeouts stay with the host. */
+PCPPX_API int pcppx_tcpstream_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                     uint8_t max_layers, const pcppx_reasm_info* info, const pcppx_tcpstream_spec* spec,
+                                     pcppx_tcpstreams* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_tcpstream_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                        const pcppx_reasm_info* info, const pcppx_tcpstream_spec* spec,
+                                        pcppx_tcpstreams* out);
+
 /* ---- frag: split the IPv4 packets of a device batch into fragments (IPFragUtil) ----
  * The inverse of defrag, for packets that sit in HBM: what Examples/IPFragUtil does with
  * splitIPPacketToFragmentsBySize (Examples/IPFragUtil/main.cpp:153-238). Every chosen IPv4 packet whose IP payload is

@@ -256,6 +256,49 @@ def defrag_reference(batch: Batch, records: Records, max_layers: int, info, spec
                                                C.byref(out)), "pcppx_defrag_reference")
 
 
+# pcppx_tcpstream_*: the TCP connection sides that are clean inside a batch (include/pcppx.h, tcpstream)
+TCPS_F_SYN, TCPS_F_FIN, TCPS_F_RST, TCPS_F_OOO = 1, 2, 4, 8  # pcppx_tcpstream_rec.flags
+TCPS_NOT_TCP, TCPS_HOST, TCPS_LEFT, TCPS_STREAM, TCPS_CONTROL, TCPS_BAD_DESC = range(6)  # disposition values
+(TCPS_STREAMS, TCPS_BYTES, TCPS_SEGMENTS, TCPS_LEFT_N, TCPS_CANDIDATES, TCPS_HOST_N, TCPS_BAD_DESC_N,
+ TCPS_OVERFLOW) = range(8)  # pcppx_tcpstreams.totals words
+TCPS_TOTALS = 8
+TCPS_NONE = 0xFFFFFFFF
+TCPS_FIELDS = ("streams", "bytes", "segments", "left", "candidates", "host", "bad_desc", "overflow")
+TCPSTREAM_DTYPE = np.dtype(
+    [("pos", "<u8"), ("bytes", "<u4"), ("flow_key", "<u4"), ("first", "<u4"), ("segments", "<u4"), ("peer", "<u4"),
+     ("side", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
+)
+assert TCPSTREAM_DTYPE.itemsize == 32
+
+
+class TcpStreamSpec(C.Structure):
+    """pcppx_tcpstream_spec: the room for candidates (0 = n) and enableBaseBufferClearCondition."""
+    _fields_ = [("max_segments", C.c_uint32), ("base_clear", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class TcpStreams(C.Structure):
+    """pcppx_tcpstreams: the stream bytes, one record per clean side, the per-source columns and the totals."""
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("streams", C.c_void_p), ("disposition", C.c_void_p),
+                ("seg_stream", C.c_void_p), ("seg_pos", C.c_void_p), ("max_streams", C.c_uint32),
+                ("reserved", C.c_uint32), ("totals", C.c_void_p)]
+
+
+def make_tcpstream_spec(base_clear: bool = True, max_segments: int = 0) -> TcpStreamSpec:
+    return TcpStreamSpec(max_segments, 1 if base_clear else 0)
+
+
+def tcpstream_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(TCPS_FIELDS)}
+
+
+def tcpstream_reference(batch: Batch, records: Records, max_layers: int, info, spec: TcpStreamSpec,
+                        out: TcpStreams) -> None:
+    """pcppx_tcpstream_reference: pcppx_tcpstream_device's contract in plain C++ over host pointers (no GPU). info: the
+    address of n pcppx_reasm_info; the structs hold addresses of host (numpy) arrays the caller keeps alive."""
+    check(load_engine().pcppx_tcpstream_reference(C.byref(batch), C.byref(records), max_layers, info, C.byref(spec),
+                                                  C.byref(out)), "pcppx_tcpstream_reference")
+
+
 # pcppx_frag_*: the IPv4 packets of a batch split into fragments (include/pcppx.h, frag)
 (FRAG_UNSELECTED, FRAG_NOT_V4, FRAG_ALREADY, FRAG_FITS, FRAG_DF, FRAG_SPLIT, FRAG_BAD_DESC) = range(7)  # disposition
 (FRAG_OUT_PACKETS, FRAG_OUT_BYTES, FRAG_SPLIT_PACKETS, FRAG_FRAGMENTS, FRAG_COPIED, FRAG_UNDER_SIZE, FRAG_BAD_DESC_N,
@@ -507,6 +550,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_defrag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P, C.POINTER(DefragSpec),
                                            C.POINTER(Defragged)]
     lib.pcppx_defrag_reference.restype = C.c_int
+    lib.pcppx_tcpstream_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P,
+                                           C.POINTER(TcpStreamSpec), C.POINTER(TcpStreams), P]
+    lib.pcppx_tcpstream_device.restype = C.c_int
+    lib.pcppx_tcpstream_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P,
+                                              C.POINTER(TcpStreamSpec), C.POINTER(TcpStreams)]
+    lib.pcppx_tcpstream_reference.restype = C.c_int
     lib.pcppx_frag_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(FragSpec),
                                       C.POINTER(Fragmented), P]
     lib.pcppx_frag_device.restype = C.c_int
@@ -540,6 +589,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
     "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_frag_device", "pcppx_frag_reference",
+    "pcppx_tcpstream_device", "pcppx_tcpstream_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

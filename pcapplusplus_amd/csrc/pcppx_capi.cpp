@@ -242,6 +242,9 @@ struct pcppx_ctx
 	Scratch steer;
 	// pcppx_defrag_device: the group table, the candidate records and the block sums (defrag_scratch_bytes)
 	Scratch defrag;
+	// pcppx_tcpstream_device: the connection and segment tables, the candidate records, the per-packet words and the
+	// block sums (tcpstream_scratch_bytes)
+	Scratch tcpstream;
 	// pcppx_frag_device: the block sums and bases and the per-packet plans (frag_scratch_bytes)
 	Scratch frag;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
@@ -920,6 +923,8 @@ extern "C"
 		c->steer.release(c->stream);
 		c->defrag.wait();
 		c->defrag.release(c->stream);
+		c->tcpstream.wait();
+		c->tcpstream.release(c->stream);
 		c->frag.wait();
 		c->frag.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
@@ -932,7 +937,7 @@ extern "C"
 			(void)hipFree(c->d_win);
 			(void)hipHostFree(c->h_win);
 		}
-		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->frag })
+		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1687,6 +1692,39 @@ extern "C"
 			pos += len;
 		}
 		return PCPPX_OK;
+	}
+}
+
+// ---- tcpstream: the TCP connection sides that are clean inside a batch (include/pcppx.h, tcpstream) ----
+namespace pcppx
+{
+// pcppx_tcpstream_ref.cpp (plain C++, beside pcppx_tcpstream_reference): the argument rules both calls share
+bool valid_tcpstream(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
+                     const pcppx_tcpstream_spec* s, const pcppx_tcpstreams* o);
+}  // namespace pcppx
+
+extern "C"
+{
+	int pcppx_tcpstream_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                           const pcppx_reasm_info* info, const pcppx_tcpstream_spec* s, pcppx_tcpstreams* o,
+	                           void* hip_stream)
+	{
+		if (c == nullptr || !pcppx::valid_tcpstream(b, r, max_layers, info, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_TCPS_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous tcpstream call (possibly queued on another stream) owns the tables until it is done
+		int rc = c->tcpstream.acquire(st, pcppx::tcpstream_scratch_bytes(b->n, s->max_segments));
+		if (rc != PCPPX_OK)
+			return rc;
+		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+		                                            : reinterpret_cast<const uint8_t*>(r->brief);
+		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+		rc = pcppx::launch_tcpstream(b, r->layers, max_layers, rec0, stride, info, s, o, c->tcpstream.ptr, st);
+		return rc != PCPPX_OK ? rc : c->tcpstream.mark_used(st);
 	}
 }
 

@@ -70,6 +70,20 @@ uint64_t defrag_scratch_bytes(uint32_t n, uint32_t max_fragments);
 int launch_defrag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
                   uint32_t nl_stride, const pcppx_reasm_info* info, const pcppx_defrag_spec* spec,
                   const pcppx_defragged* out, void* scratch, hipStream_t stream);
+// pcppx_tcpstream_device (pcppx_tcpstream.hip): two clears and nine launches on `stream` (collect, second sides, join,
+// chain, verdict, count, bases, place, emit). scratch: tcpstream_scratch_bytes(n, max_segments) bytes (include/pcppx.h
+// gives the formula); one block takes kTcpsBlockPk packets, the per-candidate kernels kTcpsCandPerBlock candidates;
+// rec0: packet 0's summary or brief (hash5 at byte 0, n_layers at 14, l4_layer at 15), rec_stride bytes apart.
+// Arguments are checked by the caller; n > 0.
+constexpr uint32_t kTcpsBlockPk = 1024;
+constexpr uint32_t kTcpsCandPerBlock = 256;
+constexpr uint32_t kTcpsMinSlots = 64;
+uint32_t tcpstream_room(uint32_t n, uint32_t max_segments);  // F: the candidates the scratch holds
+uint32_t tcpstream_slots(uint32_t room);                     // C: the connection table's and the segment table's slots
+uint64_t tcpstream_scratch_bytes(uint32_t n, uint32_t max_segments);
+int launch_tcpstream(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0,
+                     uint32_t rec_stride, const pcppx_reasm_info* info, const pcppx_tcpstream_spec* spec,
+                     const pcppx_tcpstreams* out, void* scratch, hipStream_t stream);
 // pcppx_frag_device (pcppx_frag.hip): three or four launches on `stream` (plan, bases, emit; with out->data the header
 // patch). scratch: frag_scratch_bytes(n) bytes (include/pcppx.h gives the formula); one block takes kFragBlockPk source
 // packets and puts out all of their output packets; n_layers / nl_stride as for launch_defrag. Arguments are checked

@@ -208,6 +208,27 @@ class Engine:
                                                C.byref(spec), C.byref(out), C.c_void_p(stream or 0)),
                   "pcppx_defrag_device")
 
+    def tcpstream_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, info,
+                         spec: abi.TcpStreamSpec, streams, totals, max_streams: int, out_data=None, data_cap: int = 0,
+                         disposition=None, seg_stream=None, seg_pos=None, stream: int | None = None,
+                         data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_tcpstream_device over device tensors: the TCP connection sides that are clean inside the batch
+        are reassembled into contiguous stream bytes. summary (n * 32 bytes) or brief (n * 16 bytes): the parse's
+        records, one of them; layers: FIXED, n * max_layers * 8 bytes; info: n * 16 bytes (abi.REASM_DTYPE). out_data
+        (u8, data_cap bytes; None = index-only), streams (max_streams * 32 bytes, abi.TCPSTREAM_DTYPE), disposition
+        (u8[n]) / seg_stream / seg_pos (i32[n]) optional; totals: 8 x i64 (abi.TCPS_*), overwritten. All or nothing:
+        on overflow only the totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.TcpStreams(opt(out_data), data_cap, abi.ptr(streams), opt(disposition), opt(seg_stream),
+                             opt(seg_pos), max_streams, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_tcpstream_device(self.ctx, C.byref(b), C.byref(rec), max_layers, abi.ptr(info),
+                                                  C.byref(spec), C.byref(out), C.c_void_p(stream or 0)),
+                  "pcppx_tcpstream_device")
+
     def frag_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.FragSpec,
                     out_offsets, out_caplens, totals, max_packets: int, out_data=None, data_cap: int = 0,
                     out_index=None, out_frag_no=None, counts=None, disposition=None, stream: int | None = None,
@@ -580,6 +601,51 @@ def steer_on_device(eng: Engine, batch: PacketBatch, bucket=None, key=None, key_
     if batch.frame_lens is not None:
         out.frame_lens = batch.frame_lens[index]
     return out, index, first.cpu().numpy().view(np.uint32), pos.cpu().numpy().view(np.uint64), tot
+
+
+def tcpstream_on_device(eng: Engine, batch: PacketBatch, records, layers, info, base_clear: bool = True,
+                        max_segments: int = 0, data_cap: int | None = None, max_streams: int | None = None,
+                        index_only: bool = False, device: str = "cuda:0"):
+    """Copy a host batch and its parse to HBM, reassemble there the TCP connection sides that are clean inside the
+    batch (pcppx_tcpstream_device), copy the result back: (data u8 = the stream bytes back to back; streams =
+    abi.TCPSTREAM_DTYPE records, one per clean side, ordered by the side's first packet; disposition u8[n] = abi.TCPS_*
+    per source packet; seg_stream / seg_pos u32[n]; totals dict). records: the batch's summary or brief record array;
+    layers: its FIXED [n, max_layers] layer array; info: its abi.REASM_DTYPE array (Engine.parse_reasm_device gives all
+    three in one pass). data_cap / max_streams default to the batch's bytes / packets and max_segments to n (always
+    enough). All or nothing: when totals["overflow"] is set the returned arrays are empty. The packets with
+    disposition abi.TCPS_LEFT are what the caller's host TcpReassembly (or tcpstream.Reassembler) is fed."""
+    import torch
+
+    n = batch.n
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize not in (abi.BRIEF_DTYPE.itemsize, abi.SUMMARY_DTYPE.itemsize):
+        raise ValueError("records must be a summary or a brief record array")
+    lay = np.ascontiguousarray(layers)
+    ml = lay.shape[1]
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(device)  # noqa: E731
+    pad = lambda a: a if len(a) else np.zeros(1, a.dtype)  # noqa: E731
+    data, offsets, caplens = to_device(batch, device)
+    rec_t, lay_t, info_t = up(pad(rec)), up(pad(lay.reshape(-1))), up(pad(np.ascontiguousarray(info)))
+    cap = int(batch.caplens.sum(dtype=np.uint64)) if data_cap is None else data_cap
+    ms = n if max_streams is None else max_streams
+    out_data = None if index_only else torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    streams = torch.empty(max(ms, 1) * abi.TCPSTREAM_DTYPE.itemsize, dtype=torch.uint8, device=device)
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    seg_stream = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    seg_pos = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    totals = torch.empty(abi.TCPS_TOTALS, dtype=torch.int64, device=device)
+    is_brief = rec.dtype.itemsize == abi.BRIEF_DTYPE.itemsize
+    eng.tcpstream_device(data, offsets, caplens, n, batch.linktype, lay_t, ml, info_t,
+                         abi.make_tcpstream_spec(base_clear, max_segments), streams, totals, ms, out_data, cap, disp,
+                         seg_stream, seg_pos, torch.cuda.current_stream(device).cuda_stream,
+                         summary=None if is_brief else rec_t, brief=rec_t if is_brief else None)
+    torch.cuda.synchronize(device)
+    tot = abi.tcpstream_totals_dict(totals.cpu().numpy().view(np.uint64))
+    w, wb, k = (0, 0, 0) if tot["overflow"] else (tot["streams"], tot["bytes"], n)
+    out = np.zeros(0, np.uint8) if index_only else out_data[:wb].cpu().numpy()
+    recs = streams[:w * abi.TCPSTREAM_DTYPE.itemsize].cpu().numpy().view(abi.TCPSTREAM_DTYPE)
+    return (out, recs, disp[:k].cpu().numpy(), seg_stream[:k].cpu().numpy().view(np.uint32),
+            seg_pos[:k].cpu().numpy().view(np.uint32), tot)
 
 
 def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, passthrough: bool = True,
