@@ -925,6 +925,132 @@ PCPPX_API int pcppx_frag_device(pcppx_ctx* ctx, const pcppx_batch* batch, const 
 PCPPX_API int pcppx_frag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                    const pcppx_frag_spec* spec, pcppx_fragmented* out);
 
+/* ---- tlsfp: JA3 / JA3S TLS fingerprints of the hello packets of a device batch (TLSFingerprinting) ----
+ * What Examples/TLSFingerprinting does with SSLClientHelloMessage::generateTLSFingerprint() and
+ * SSLServerHelloMessage::generateTLSFingerprint() and their toStringAndMD5() (Packet++/src/SSLHandshake.cpp:1577-1689,
+ * 1892-1950; Examples/TLSFingerprinting/main.cpp:328-381), for packets that sit in HBM: per ClientHello / ServerHello
+ * packet one record with the fingerprint text's MD5, the text itself and the packet's number (which indexes
+ * pcppx_tuple for the addresses and ports of the example's output file; md5's first word is a 32-bit key for
+ * pcppx_steer_device or pcppx_flow_count_keys_device). Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * Inputs: as frag. A device batch and its FIXED records (max_layers >= 1, the same value as the parse used; the summary
+ * or, when it is NULL, the brief supplies flags and n_layers; PACKED and DENSE records are refused). No
+ * pcppx_reasm_info is needed.
+ *
+ * Per packet i the first rule that applies decides (be16(x): the big-endian 16-bit word at byte x):
+ *   1 BAD_DESC. offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (the rule of select, steer, defrag and
+ *     frag): the packet is never read.
+ *   2 The handshake layer: the first entry k < min(n_layers, max_layers) with proto == 18 (pcpp::SSL) that lies inside
+ *     the packet (data_len >= 5, hdr_len >= 5, hdr_len <= data_len, offset + data_len <= caplen) and whose byte at
+ *     `offset` is 22: getLayerOfType<SSLHandshakeLayer>() (SSLLayer.cpp:42-56, main.cpp:335). An entry that points
+ *     outside the packet is never followed. R = hdr_len - 5 is the record's data length as the constructor clamps it
+ *     (SSLLayer.cpp:126-136). Only this layer is looked at: a hello in a later handshake record is not found, as in the
+ *     reference.
+ *   3 No handshake layer: HOST when the chain may hold one the device did not record -- flags has
+ *     PCPPX_F_NEEDS_HOST_PROTO, OVERSIZE, BAD_DESC or DEPTH_OVERFLOW, or n_layers > max_layers, or NEEDS_HOST_L7 is set
+ *     with L7_SSL set or without L7_KNOWN. Otherwise NONE (a parse-until option that cut the chain short is the caller's
+ *     choice).
+ *   4 Messages (SSLLayer.cpp:138-149, SSLHandshake.cpp:1287-1350, 2257-2262): cur = 0; loop: D = R - cur, stop when
+ *     D < 4; the message starts at offset + 5 + cur; it is unknown, takes all of D and ends the walk when D >= 16 and
+ *     either its first five bytes are zero or its byte 1 is >= 1; otherwise its type is byte 0 and its length
+ *     M = min(4 + be16(2), D); cur += M. With spec->client the first message of type 1 makes the packet CLIENT;
+ *     otherwise, with spec->server, the first message of type 2 makes it SERVER (ClientHello wins when a record holds
+ *     both, main.cpp:339-377); otherwise NONE. Below, byte positions count from the message's first byte, and the
+ *     bound of every field read is D, the rest of the record, not M; only the extension list is cut at M.
+ *   5 Shared pieces. Session id: sid = D <= 39 ? 0 : min(byte 38, D - 39). Extension list at E
+ *     (SSLHandshake.cpp:1366-1449, 1695-1773, SSLHandshake.h:151-165): none when E + 2 > D; otherwise it = E + 2,
+ *     end = min(it + be16(E), M), and while end - it >= 4 (as signed numbers): type = be16(it), len = be16(it + 2); stop
+ *     when end - it < 4 + len; append (type, data at it + 4, len); it += 4 + len. GREASE: a 16-bit value whose two
+ *     bytes are equal with low nibble 0xA (the set at SSLHandshake.cpp:1040-1053).
+ *   6 ClientHello text (SSLHandshake.cpp:1451-1527, 1577-1677): "version,ciphers,extensions,groups,formats", every
+ *     number unsigned decimal without padding, lists joined by '-', empty lists empty. version = D < 6 ? 0 : be16(4).
+ *     cs = 39 + sid, count = cs + 2 > D ? 0 : be16(cs) / 2; cipher entry i < count is used while
+ *     cs + 2 + 2 (i + 1) <= D, GREASE removed. E = cs + 2 + 2 count + 2: the reference assumes exactly one compression
+ *     method and uses count, not the number of valid entries; both quirks are kept. Extensions: the types, GREASE
+ *     removed. Groups: of the first listed extension of type 10, used only when len >= 2, be16(data) == len - 2 and that
+ *     value is even; GREASE removed. Formats: of the first listed extension of type 11, used only when len >= 1 and
+ *     len == data[0] + 1; one decimal per byte. Both are searched in the unfiltered list.
+ *   7 ServerHello text (SSLHandshake.cpp:1775-1940): "version,cipher,extensions". cipher = 39 + sid + 2 > D ? 0 :
+ *     be16(39 + sid); E = 39 + sid + 3; the extension types are not GREASE-filtered. version: of the first listed
+ *     extension of type 43, len == 2 gives be16(data), len == 3 with data[0] == 2 gives be16(data + 1); otherwise
+ *     D < 6 ? 0 : be16(4). One deliberate departure: with that extension at len == 0 the reference dereferences a null
+ *     getData(); here the header's version is used.
+ *   8 md5 is the RFC 1321 digest of the text's bytes. */
+typedef struct pcppx_tlsfp_spec {
+	uint32_t max_hellos; /* the hello packets the call has room for; 0 = n (always enough) */
+	uint8_t client;      /* 0 / 1: ClientHello fingerprints (the example's -t ch) */
+	uint8_t server;      /* 0 / 1: ServerHello fingerprints (-t sh); both = ch_sh; at least one */
+	uint8_t reserved[2];
+} pcppx_tlsfp_spec;
+
+#define PCPPX_TLSFP_CLIENT 1 /* pcppx_tlsfp_rec.kind (and the disposition of its packet) */
+#define PCPPX_TLSFP_SERVER 2
+typedef struct pcppx_tlsfp_rec { /* 40 bytes per fingerprint */
+	uint8_t md5[16];     /* RFC 1321 digest of the text; md5[0] is the first byte of toMD5()'s hex string */
+	uint64_t text_pos;   /* byte position of the text in out->text */
+	uint32_t text_len;
+	uint32_t index;      /* source packet number (strictly ascending) */
+	uint16_t msg_offset; /* the hello message's first byte, from the packet's first byte (its low 16 bits, where
+	                        crafted records place the layer past byte 65,535 of an oversize packet) */
+	uint8_t kind;        /* PCPPX_TLSFP_CLIENT / PCPPX_TLSFP_SERVER */
+	uint8_t reserved[5]; /* written as 0 */
+} pcppx_tlsfp_rec;
+
+/* pcppx_tlsfps.disposition values */
+#define PCPPX_TLSFP_NONE 0     /* no hello the spec asks for (in bounds) */
+/*      PCPPX_TLSFP_CLIENT 1      a record of kind CLIENT */
+/*      PCPPX_TLSFP_SERVER 2      a record of kind SERVER */
+#define PCPPX_TLSFP_HOST 3     /* no recorded handshake layer, but the host's chain may hold one (rule 3) */
+#define PCPPX_TLSFP_BAD_DESC 4 /* the descriptor is out of bounds: never read */
+
+/* pcppx_tlsfps.totals words */
+#define PCPPX_TLSFP_CLIENT_N 0
+#define PCPPX_TLSFP_SERVER_N 1
+#define PCPPX_TLSFP_TEXT_BYTES 2
+#define PCPPX_TLSFP_HOST_N 3
+#define PCPPX_TLSFP_BAD_DESC_N 4
+#define PCPPX_TLSFP_CANDIDATES 5 /* hello packets: CLIENT_N + SERVER_N */
+/* word 6 is zero */
+#define PCPPX_TLSFP_OVERFLOW 7
+#define PCPPX_TLSFP_TOTALS 8
+
+typedef struct pcppx_tlsfps {  /* device pointers; host pointers for pcppx_tlsfp_reference */
+	pcppx_tlsfp_rec* recs;     /* max_recs entries, in source order */
+	uint8_t* text;             /* the fingerprint texts back to back in record order, no terminator; NULL = MD5 only */
+	uint64_t text_cap;
+	uint8_t* disposition;      /* optional (NULL): n entries, PCPPX_TLSFP_* per source packet */
+	uint32_t max_recs;
+	uint32_t reserved;
+	uint64_t* totals;          /* PCPPX_TLSFP_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_tlsfps;
+
+/* Capacity is all or nothing, as in frag and defrag: OVERFLOW = 1 iff CLIENT_N + SERVER_N > max_recs, or text != NULL
+ * and TEXT_BYTES > text_cap, or CANDIDATES > max_hellos (0 = n). Then only the totals are written (no record, no byte
+ * of text, no disposition): they hold the full would-be values, except that with CANDIDATES > max_hellos only
+ * CANDIDATES, HOST_N, BAD_DESC_N and OVERFLOW are given (the other words are 0). With text == NULL the digests are
+ * still computed, text_pos holds the would-be positions and the byte capacity is not applied. Sizing: a call with
+ * max_recs = 0 overflows and gives CLIENT_N + SERVER_N and TEXT_BYTES; or use the closed bound
+ * text_len <= 4 * caplen + 16 (a point-format byte prints as at most 4 characters, two list bytes as at most 6).
+ * One packet may hold ~32k cipher entries and make one lane walk ~190 KB of text while its wave waits: the cost of a
+ * hello is bounded by PCPPX_MAX_CAPLEN bytes of it, as in the reference.
+ * Source bytes are read only from in-bounds packets, inside a recorded SSL layer that lies inside the packet. Nothing
+ * is written outside the first CLIENT_N + SERVER_N records, [0, TEXT_BYTES) of the text and the n dispositions. The
+ * output is a pure function of the inputs, bit-identical from run to run: positions come from counts and scans, and
+ * there are no atomics. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals or recs; with n > 0 a null
+ * records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS; client and server both 0, or either above 1; a non-zero reserved field. The work is queued on
+ * hip_stream and the call returns without waiting; calls on one context are ordered through its tlsfp scratch (a buffer
+ * and an event of their own, as frag's). Scratch: with g = ceil(n / 1024) blocks, 48 g + 16 n bytes (per block its
+ * records and text bytes and their exclusive prefixes, 64-bit each, and four 32-bit counts; per packet a 16-byte plan:
+ * the message's offset, D, M, the text's length and the disposition); PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_tlsfp_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                 uint8_t max_layers, const pcppx_tlsfp_spec* spec, pcppx_tlsfps* out,
+                                 void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_tlsfp_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                    const pcppx_tlsfp_spec* spec, pcppx_tlsfps* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

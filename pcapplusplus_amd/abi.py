@@ -338,6 +338,52 @@ def frag_reference(batch: Batch, records: Records, max_layers: int, spec: FragSp
                                              C.byref(out)), "pcppx_frag_reference")
 
 
+# pcppx_tlsfp_*: JA3 / JA3S fingerprints of the hello packets of a batch (include/pcppx.h, tlsfp)
+TLSFP_NONE, TLSFP_CLIENT, TLSFP_SERVER, TLSFP_HOST, TLSFP_BAD_DESC = range(5)  # disposition; CLIENT / SERVER: rec.kind
+(TLSFP_CLIENT_N, TLSFP_SERVER_N, TLSFP_TEXT_BYTES, TLSFP_HOST_N, TLSFP_BAD_DESC_N, TLSFP_CANDIDATES, _TLSFP_ZERO,
+ TLSFP_OVERFLOW) = range(8)  # pcppx_tlsfps.totals words
+TLSFP_TOTALS = 8
+TLSFP_FIELDS = ("client_n", "server_n", "text_bytes", "host_n", "bad_desc", "candidates", "zero", "overflow")
+TLSFP_REC_DTYPE = np.dtype(
+    [("md5", "u1", (16,)), ("text_pos", "<u8"), ("text_len", "<u4"), ("index", "<u4"), ("msg_offset", "<u2"),
+     ("kind", "u1"), ("reserved", "u1", (5,))]
+)
+assert TLSFP_REC_DTYPE.itemsize == 40
+
+
+class TlsfpSpec(C.Structure):
+    """pcppx_tlsfp_spec: the room for hello packets (0 = n) and which hellos are fingerprinted."""
+    _fields_ = [("max_hellos", C.c_uint32), ("client", C.c_uint8), ("server", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class TlsfpRec(C.Structure):
+    """pcppx_tlsfp_rec (TLSFP_REC_DTYPE is its numpy mirror)."""
+    _fields_ = [("md5", C.c_uint8 * 16), ("text_pos", C.c_uint64), ("text_len", C.c_uint32), ("index", C.c_uint32),
+                ("msg_offset", C.c_uint16), ("kind", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class Tlsfps(C.Structure):
+    """pcppx_tlsfps: the records, the texts back to back, the per-source disposition and the totals."""
+    _fields_ = [("recs", C.c_void_p), ("text", C.c_void_p), ("text_cap", C.c_uint64), ("disposition", C.c_void_p),
+                ("max_recs", C.c_uint32), ("reserved", C.c_uint32), ("totals", C.c_void_p)]
+
+
+def make_tlsfp_spec(client: bool = True, server: bool = True, max_hellos: int = 0) -> TlsfpSpec:
+    """client / server: the example's -t ch / sh / ch_sh."""
+    return TlsfpSpec(max_hellos, 1 if client else 0, 1 if server else 0)
+
+
+def tlsfp_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(TLSFP_FIELDS)}
+
+
+def tlsfp_reference(batch: Batch, records: Records, max_layers: int, spec: TlsfpSpec, out: Tlsfps) -> None:
+    """pcppx_tlsfp_reference: pcppx_tlsfp_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_tlsfp_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                              C.byref(out)), "pcppx_tlsfp_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -562,6 +608,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_frag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(FragSpec),
                                          C.POINTER(Fragmented)]
     lib.pcppx_frag_reference.restype = C.c_int
+    lib.pcppx_tlsfp_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(TlsfpSpec),
+                                       C.POINTER(Tlsfps), P]
+    lib.pcppx_tlsfp_device.restype = C.c_int
+    lib.pcppx_tlsfp_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(TlsfpSpec),
+                                          C.POINTER(Tlsfps)]
+    lib.pcppx_tlsfp_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -589,7 +641,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
     "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_frag_device", "pcppx_frag_reference",
-    "pcppx_tcpstream_device", "pcppx_tcpstream_reference",
+    "pcppx_tcpstream_device", "pcppx_tcpstream_reference", "pcppx_tlsfp_device", "pcppx_tlsfp_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

@@ -19,6 +19,7 @@
 
 #include "pcppx.h"
 #include "pcppx_internal.h"
+#include "pcppx_tlsfp.h"
 
 namespace
 {
@@ -247,6 +248,8 @@ struct pcppx_ctx
 	Scratch tcpstream;
 	// pcppx_frag_device: the block sums and bases and the per-packet plans (frag_scratch_bytes)
 	Scratch frag;
+	// pcppx_tlsfp_device: the per-packet plans and the block sums and bases (tlsfp_scratch_bytes)
+	Scratch tlsfp;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -927,6 +930,8 @@ extern "C"
 		c->tcpstream.release(c->stream);
 		c->frag.wait();
 		c->frag.release(c->stream);
+		c->tlsfp.wait();
+		c->tlsfp.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -937,7 +942,8 @@ extern "C"
 			(void)hipFree(c->d_win);
 			(void)hipHostFree(c->h_win);
 		}
-		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag })
+		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag,
+		                         &c->tlsfp })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1725,6 +1731,32 @@ extern "C"
 		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
 		rc = pcppx::launch_tcpstream(b, r->layers, max_layers, rec0, stride, info, s, o, c->tcpstream.ptr, st);
 		return rc != PCPPX_OK ? rc : c->tcpstream.mark_used(st);
+	}
+}
+
+// ---- tlsfp: JA3 / JA3S fingerprints of the hello packets of a batch (include/pcppx.h, tlsfp) ----
+// pcppx_tlsfp_reference is pcppx_tlsfp_ref.cpp (plain C++); the argument rules both calls share are pcppx_tlsfp.h's
+extern "C"
+{
+	int pcppx_tlsfp_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                       const pcppx_tlsfp_spec* s, pcppx_tlsfps* o, void* hip_stream)
+	{
+		if (c == nullptr || !pcppx::tlsfp::valid_args(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_TLSFP_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous tlsfp call (possibly queued on another stream) owns the plans until it is done
+		int rc = c->tlsfp.acquire(st, pcppx::tlsfp_scratch_bytes(b->n));
+		if (rc != PCPPX_OK)
+			return rc;
+		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+		                                            : reinterpret_cast<const uint8_t*>(r->brief);
+		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+		rc = pcppx::launch_tlsfp(b, r->layers, max_layers, rec0, stride, s, o, c->tlsfp.ptr, st);
+		return rc != PCPPX_OK ? rc : c->tlsfp.mark_used(st);
 	}
 }
 

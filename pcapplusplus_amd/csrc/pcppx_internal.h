@@ -94,6 +94,14 @@ uint64_t frag_scratch_bytes(uint32_t n);
 int launch_frag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
                 uint32_t nl_stride, const pcppx_frag_spec* spec, const pcppx_fragmented* out, void* scratch,
                 hipStream_t stream);
+// pcppx_tlsfp_device (pcppx_tlsfp.hip): three launches on `stream` (plan, bases, emit). scratch: tlsfp_scratch_bytes(n)
+// bytes (include/pcppx.h gives the formula); one block takes kTlsfpBlockPk source packets and writes their records;
+// rec0: packet 0's summary or brief, rec_stride bytes apart. Arguments are checked by the caller; n > 0.
+constexpr uint32_t kTlsfpBlockPk = 1024;
+uint32_t tlsfp_blocks(uint32_t n);
+uint64_t tlsfp_scratch_bytes(uint32_t n);
+int launch_tlsfp(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
+                 const pcppx_tlsfp_spec* spec, const pcppx_tlsfps* out, void* scratch, hipStream_t stream);
 // pcppx_bpf_device (pcppx_bpf.hip): one launch on `stream` (the caller has cleared out->totals on it). insns: the
 // validated programs back to back in device memory; program p is insns[start[p] .. start[p + 1]); uses_mem: bit p set
 // when program p loads from M[] (only then are its slots cleared). Arguments are checked by the caller; n > 0.

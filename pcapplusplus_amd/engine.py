@@ -250,6 +250,23 @@ class Engine:
         abi.check(self.lib.pcppx_frag_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_frag_device")
 
+    def tlsfp_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int,
+                     spec: abi.TlsfpSpec, recs, totals, max_recs: int, text=None, text_cap: int = 0, disposition=None,
+                     stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_tlsfp_device over device tensors: one record (abi.TLSFP_REC_DTYPE, 40 bytes) per ClientHello /
+        ServerHello packet spec asks for, with the MD5 of its JA3 / JA3S text. summary (n * 32 bytes) or brief (n * 16
+        bytes): the parse's records, one of them; layers: FIXED, n * max_layers * 8 bytes. recs: max_recs * 40 bytes;
+        text (u8, text_cap bytes; None = MD5 only); disposition (u8[n], optional); totals: 8 x i64 (abi.TLSFP_*),
+        overwritten. All or nothing: on overflow only the totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.Tlsfps(abi.ptr(recs), opt(text), text_cap, opt(disposition), max_recs, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_tlsfp_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_tlsfp_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -770,6 +787,43 @@ def frag_on_device(eng: Engine, batch: PacketBatch, records, layers, frag_size: 
         split = dispo[index] == abi.FRAG_SPLIT if w else np.zeros(0, bool)
         out.frame_lens = np.where(split, out.caplens, batch.frame_lens[index]).astype(np.uint32)
     return out, index, frag_no, dispo, tot
+
+
+def tlsfp_on_device(eng: Engine, batch: PacketBatch, client: bool = True, server: bool = True,
+                    opts: abi.Opts | None = None, want_text: bool = True, device: str = "cuda:0"):
+    """Copy a host batch to HBM, parse it there and fingerprint its TLS hellos (pcppx_tlsfp_device) without the records
+    leaving the device in between; copy the result back: (recs abi.TLSFP_REC_DTYPE[k] in source order, text u8 = the
+    fingerprint texts back to back (empty with want_text = False), tuples abi.TUPLE_DTYPE[n] = the parse's 5-tuple
+    extracts that recs["index"] indexes, disposition u8[n] = abi.TLSFP_* per source packet, totals dict). The buffers
+    are sized by a first call with max_recs = 0, which overflows and writes the totals alone."""
+    import torch
+
+    opts = opts or abi.make_opts()
+    n, ml = batch.n, opts.max_layers
+    data, offsets, caplens = to_device(batch, device)
+    summary = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=device)
+    layers = torch.zeros(max(n * ml, 1) * 8, dtype=torch.uint8, device=device)
+    tuples = torch.zeros(max(n, 1) * 48, dtype=torch.uint8, device=device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, st, tuples=tuples)
+    spec = abi.make_tlsfp_spec(client, server)
+    totals = torch.empty(abi.TLSFP_TOTALS, dtype=torch.int64, device=device)
+
+    def call(recs, max_recs, text=None, cap=0, disp=None):
+        eng.tlsfp_device(data, offsets, caplens, n, batch.linktype, layers, ml, spec, recs, totals, max_recs, text, cap,
+                         disp, st, summary=summary)
+        torch.cuda.synchronize(device)
+        return abi.tlsfp_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    need = call(torch.empty(40, dtype=torch.uint8, device=device), 0)
+    k, nb = need["client_n"] + need["server_n"], need["text_bytes"]
+    recs = torch.empty(max(k, 1) * 40, dtype=torch.uint8, device=device)
+    text = torch.empty(max(nb, 1), dtype=torch.uint8, device=device) if want_text else None
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(recs, k, text, nb, disp)
+    assert tot["overflow"] == 0
+    return (recs.cpu().numpy().view(abi.TLSFP_REC_DTYPE)[:k], text[:nb].cpu().numpy() if want_text else
+            np.zeros(0, np.uint8), tuples.cpu().numpy().view(abi.TUPLE_DTYPE)[:n], disp[:n].cpu().numpy(), tot)
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
