@@ -1051,6 +1051,153 @@ PCPPX_API int pcppx_tlsfp_device(pcppx_ctx* ctx, const pcppx_batch* batch, const
 PCPPX_API int pcppx_tlsfp_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                     const pcppx_tlsfp_spec* spec, pcppx_tlsfps* out);
 
+/* ---- dns: DnsLayer's resource records of the DNS packets of a device batch ----
+ * What DnsLayer::parseResources and IDnsResource::decodeName do (Packet++/src/DnsLayer.cpp:133-220,
+ * DnsResource.cpp:33-155), for packets that sit in HBM: per DNS packet one message record, per linked query / answer /
+ * authority / additional resource one record with its decoded name. It is what the dns mode of
+ * Examples/PcapPlusPlus-benchmark/benchmark.cpp:30-52 walks. Added within ABI 7: new symbols only (PCPPX_ABI_VERSION
+ * stays 7).
+ *
+ * Inputs: as tlsfp. A device batch and its FIXED records (max_layers >= 1, the same value as the parse used; the summary
+ * or, when it is NULL, the brief supplies flags and n_layers; PACKED and DENSE records are refused).
+ *
+ * Per packet i the first rule that applies decides (be16(x): the big-endian 16-bit word at byte x):
+ *   1 BAD_DESC. offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (the rule of select, steer, defrag, frag and
+ *     tlsfp): the packet is never read.
+ *   2 The DNS layer: the first entry k < min(n_layers, max_layers) with proto == 13 (pcpp::DNS):
+ *     getLayerOfType<DnsLayer>(). L = data_len (m_DataLen). adj = 2 when k >= 1 and entry k - 1 has proto == 4 (TCP):
+ *     DnsOverTcpLayer (DnsLayer.h:439-441, TcpLayer.cpp:411-415), otherwise 0. The entry is followed only when it lies
+ *     inside the packet (hdr_len <= data_len and offset + data_len <= caplen) and L >= 12 + adj; otherwise the packet is
+ *     NONE and no later entry is looked at (a parse of this batch never writes such an entry).
+ *   3 No entry with proto == 13: HOST when the host's chain may hold a DNS layer the device did not record -- flags has
+ *     PCPPX_F_NEEDS_HOST_PROTO, OVERSIZE, BAD_DESC or DEPTH_OVERFLOW, or n_layers > max_layers, or NEEDS_HOST_L7 is set
+ *     with L7_DNS set or without L7_KNOWN. Otherwise NONE.
+ *   4 The message (DnsLayer.cpp:133-220); positions count from the layer's first byte. id = be16(adj), flags =
+ *     be16(adj + 2); the four declared counts are be16 at adj + 4, 6, 8 and 10. If their sum is above 300 no resource is
+ *     linked: status TOO_MANY. Otherwise off = 12 + adj and, for each of sum resources: its section is the first of
+ *     query, answer, authority, additional whose count is still non-zero (which is then decremented); name_len and the
+ *     text come from rule 5 at off; a query has size = name_len + 4; any other resource has size = name_len + 10 + dl
+ *     with dl = 0 when off + name_len + 8 >= L - 1 (DnsResource.cpp:281-295), else be16(off + name_len + 8). If
+ *     off + size > L the walk stops with status TRUNCATED, and that resource and all after it are not linked; otherwise
+ *     the resource is linked and off += size. type, class, TTL and dl of a linked resource are read at off + name_len
+ *     (in bounds by the size check). A name whose decode fails has name_len 0 and an empty name; its resource is still
+ *     linked when its 4 / 10 bytes fit, as in the reference.
+ *   5 decodeName (DnsResource.cpp:33-155) at position off, level 1 (its `iteration` argument starts at 1,
+ *     DnsResource.h:43), with all its quirks. A level is empty (name_len 0, no failure) when off + 1 > L or level > 20:
+ *     a name is its own labels and at most 19 pointers deep. Otherwise enc = 0, cur = off, and while byte w at cur is not 0:
+ *       a pointer (w & 0xC0 == 0xC0): if cur + 2 > L or enc > 255 the level ends as with a zero byte. Otherwise
+ *         to = ((w & 0x3F) << 8 | byte(cur + 1)) + adj, modulo 2^16; to < 12 or to >= L makes the level fail (name_len 0;
+ *         the text it gathered so far stays, which matters for a nested level); otherwise the level below (at `to`,
+ *         level + 1) is decoded, its text is cut at its first NUL byte, and as much of it as leaves this level's text at
+ *         255 bytes or less is appended; name_len = enc + 2, and no trailing dot is removed.
+ *       a label (every other w, 0x40-0xBF included): if cur + w + 1 > L or enc + w > 255 the level ends cut: with
+ *         enc == 256 its last text byte is dropped and name_len = 256, else name_len = enc + 1 and the text keeps its
+ *         trailing dot. Otherwise the label's w bytes and a '.' join the text, cur and enc grow by w + 1, and if then
+ *         cur + 1 > L the level ends cut in the same way.
+ *     At the zero byte (cleanup()): the text loses its last byte (the dot) when it has one, and name_len = enc + 1, or
+ *     enc when the text had 256 bytes. Every level counts its own enc. The resource's name is empty when level 1 failed
+ *     or name_len is 0; otherwise it is the text up to its first NUL byte (std::string from a C string): at most 255
+ *     bytes (text_len <= 511 is a safe bound). The implementation has no recursion: after a pointer a level only
+ *     returns, so a name is a chain of at most 20 label runs under one running byte budget. */
+typedef struct pcppx_dns_spec {
+	uint32_t max_msgs;   /* the DNS packets the call has room for; 0 = n (always enough) */
+	uint8_t sections;    /* bits 0-3: resource records of queries, answers, authorities, additionals; non-zero */
+	uint8_t reserved[3];
+} pcppx_dns_spec;
+
+#define PCPPX_DNS_QUERY 0 /* pcppx_dns_rr.section, and the index into declared[] / linked[] */
+#define PCPPX_DNS_ANSWER 1
+#define PCPPX_DNS_AUTHORITY 2
+#define PCPPX_DNS_ADDITIONAL 3
+
+/* pcppx_dns_msg.status */
+#define PCPPX_DNS_COMPLETE 0  /* every declared resource is linked */
+#define PCPPX_DNS_TRUNCATED 1 /* a resource reached past the layer's end: it and all after it are not linked */
+#define PCPPX_DNS_TOO_MANY 2  /* more than 300 declared resources: none is linked */
+
+typedef struct pcppx_dns_msg { /* 40 bytes per DNS packet */
+	uint64_t first_rr;     /* record number in out->rrs of its first resource record */
+	uint32_t index;        /* source packet number (strictly ascending) */
+	uint16_t layer_offset; /* the DNS layer's first byte, from the packet's first byte */
+	uint16_t layer_len;    /* L */
+	uint16_t id;           /* be16(adj): dnshdr.transactionID */
+	uint16_t flags;        /* be16(adj + 2): the header's flag bits as one big-endian word */
+	uint16_t declared[4];  /* the header's four counts */
+	uint16_t linked[4];    /* the resources linked per section, whatever spec->sections says */
+	uint16_t n_rr;         /* the resource records emitted for it: linked[] of the sections in spec->sections */
+	uint8_t adjust;        /* adj: 2 for DNS over TCP, else 0 */
+	uint8_t status;        /* PCPPX_DNS_COMPLETE / TRUNCATED / TOO_MANY */
+} pcppx_dns_msg;
+
+typedef struct pcppx_dns_rr { /* 32 bytes per linked resource of a section in spec->sections, in walk order */
+	uint64_t name_pos;    /* byte position of the decoded name in out->names */
+	uint32_t msg;         /* its message's record number in out->msgs */
+	uint32_t ttl;         /* DnsResource::getTTL(); 0 for a query */
+	uint16_t offset;      /* m_OffsetInLayer: the resource's first byte, from the layer's first byte */
+	uint16_t name_len;    /* m_NameLength: the encoded name's bytes as decodeName counts them */
+	uint16_t text_len;    /* bytes of the decoded name (getName().size()) */
+	uint16_t type;        /* getDnsType() */
+	uint16_t dns_class;   /* getDnsClass() */
+	uint16_t data_len;    /* getDataLength(); 0 for a query */
+	uint16_t data_offset; /* getDataOffset(): offset + name_len + 10; 0 for a query */
+	uint8_t section;      /* PCPPX_DNS_QUERY .. PCPPX_DNS_ADDITIONAL */
+	uint8_t reserved;     /* written as 0 */
+} pcppx_dns_rr;
+
+/* pcppx_dns_out.disposition values */
+#define PCPPX_DNS_NONE 0     /* no DNS layer that is followed (in bounds) */
+#define PCPPX_DNS_MSG 1      /* a message record */
+#define PCPPX_DNS_HOST 2     /* no recorded DNS layer, but the host's chain may hold one (rule 3) */
+#define PCPPX_DNS_BAD_DESC 3 /* the descriptor is out of bounds: never read */
+
+/* pcppx_dns_out.totals words */
+#define PCPPX_DNS_MSGS 0
+#define PCPPX_DNS_RRS 1
+#define PCPPX_DNS_NAME_BYTES 2
+#define PCPPX_DNS_HOST_N 3
+#define PCPPX_DNS_BAD_DESC_N 4
+#define PCPPX_DNS_QA_LINKED 5 /* linked queries + answers of all messages, whatever spec->sections says: the number
+                                 `benchmark <file> dns 1` prints */
+/* word 6 is zero */
+#define PCPPX_DNS_OVERFLOW 7
+#define PCPPX_DNS_TOTALS 8
+
+typedef struct pcppx_dns_out { /* device pointers; host pointers for pcppx_dns_reference */
+	pcppx_dns_msg* msgs;       /* max_msgs entries, in source order */
+	pcppx_dns_rr* rrs;         /* max_rrs entries: message by message, each in walk order */
+	uint8_t* names;            /* the decoded names back to back in record order, no terminator; NULL = no text */
+	uint64_t names_cap;
+	uint8_t* disposition;      /* optional (NULL): n entries, PCPPX_DNS_* per source packet */
+	uint32_t max_msgs;
+	uint32_t max_rrs;
+	uint64_t* totals;          /* PCPPX_DNS_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_dns_out;
+
+/* Capacity is all or nothing, as in tlsfp: OVERFLOW = 1 iff MSGS > out->max_msgs, or RRS > max_rrs, or names != NULL
+ * and NAME_BYTES > names_cap, or MSGS > spec->max_msgs (0 = n). Then only the totals are written (no record, no byte of
+ * a name, no disposition); they always hold the full would-be values. With names == NULL positions and lengths are
+ * still filled and the byte capacity is not applied. Sizing: a call with max_msgs = max_rrs = 0 overflows and gives
+ * MSGS, RRS and NAME_BYTES. The cost of a packet is bounded: at most 300 resources, 20 label runs each, inside the
+ * layer's L bytes.
+ * Source bytes are read only from in-bounds packets, inside a recorded DNS layer that lies inside the packet. Nothing
+ * is written outside the first MSGS messages, the first RRS records, [0, NAME_BYTES) of names and the n dispositions.
+ * The output is a pure function of the inputs, bit-identical from run to run: positions come from counts and scans, and
+ * there are no atomics. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals, msgs or rrs; with n > 0 a null
+ * records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS; sections 0 or above 15; a non-zero reserved field. The work is queued on hip_stream and the call
+ * returns without waiting; calls on one context are ordered through its dns scratch (a buffer and an event of their
+ * own, as tlsfp's). Scratch: with g = ceil(n / 1024) blocks, 48 g + 16 n bytes (per block six 32-bit sums -- its
+ * messages, records, name bytes, HOST and BAD_DESC packets, queries plus answers -- and the 64-bit exclusive prefixes
+ * of the first three; per packet a 16-byte plan: the layer's offset, length and adjustment, the records and name bytes
+ * of the message, its queries plus answers, and the disposition);
+ * PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_dns_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                               uint8_t max_layers, const pcppx_dns_spec* spec, pcppx_dns_out* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_dns_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                  const pcppx_dns_spec* spec, pcppx_dns_out* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

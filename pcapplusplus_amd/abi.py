@@ -384,6 +384,69 @@ def tlsfp_reference(batch: Batch, records: Records, max_layers: int, spec: Tlsfp
                                               C.byref(out)), "pcppx_tlsfp_reference")
 
 
+# pcppx_dns_*: DnsLayer's resource records of the DNS packets of a batch (include/pcppx.h, dns)
+DNS_NONE, DNS_MSG, DNS_HOST, DNS_BAD_DESC = range(4)            # disposition
+DNS_QUERY, DNS_ANSWER, DNS_AUTHORITY, DNS_ADDITIONAL = range(4)  # rr.section
+DNS_COMPLETE, DNS_TRUNCATED, DNS_TOO_MANY = range(3)             # msg.status
+(DNS_MSGS, DNS_RRS, DNS_NAME_BYTES, DNS_HOST_N, DNS_BAD_DESC_N, DNS_QA_LINKED, _DNS_ZERO,
+ DNS_OVERFLOW) = range(8)  # pcppx_dns_out.totals words
+DNS_TOTALS = 8
+DNS_FIELDS = ("msgs", "rrs", "name_bytes", "host_n", "bad_desc", "qa_linked", "zero", "overflow")
+DNS_MSG_DTYPE = np.dtype(
+    [("first_rr", "<u8"), ("index", "<u4"), ("layer_offset", "<u2"), ("layer_len", "<u2"), ("id", "<u2"),
+     ("flags", "<u2"), ("declared", "<u2", (4,)), ("linked", "<u2", (4,)), ("n_rr", "<u2"), ("adjust", "u1"),
+     ("status", "u1")]
+)
+DNS_RR_DTYPE = np.dtype(
+    [("name_pos", "<u8"), ("msg", "<u4"), ("ttl", "<u4"), ("offset", "<u2"), ("name_len", "<u2"), ("text_len", "<u2"),
+     ("type", "<u2"), ("dns_class", "<u2"), ("data_len", "<u2"), ("data_offset", "<u2"), ("section", "u1"),
+     ("reserved", "u1")]
+)
+assert DNS_MSG_DTYPE.itemsize == 40 and DNS_RR_DTYPE.itemsize == 32
+
+
+class DnsSpec(C.Structure):
+    """pcppx_dns_spec: the room for DNS packets (0 = n) and the sections whose resources get records."""
+    _fields_ = [("max_msgs", C.c_uint32), ("sections", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class DnsMsg(C.Structure):
+    """pcppx_dns_msg (DNS_MSG_DTYPE is its numpy mirror)."""
+    _fields_ = [("first_rr", C.c_uint64), ("index", C.c_uint32), ("layer_offset", C.c_uint16),
+                ("layer_len", C.c_uint16), ("id", C.c_uint16), ("flags", C.c_uint16), ("declared", C.c_uint16 * 4),
+                ("linked", C.c_uint16 * 4), ("n_rr", C.c_uint16), ("adjust", C.c_uint8), ("status", C.c_uint8)]
+
+
+class DnsRr(C.Structure):
+    """pcppx_dns_rr (DNS_RR_DTYPE is its numpy mirror)."""
+    _fields_ = [("name_pos", C.c_uint64), ("msg", C.c_uint32), ("ttl", C.c_uint32), ("offset", C.c_uint16),
+                ("name_len", C.c_uint16), ("text_len", C.c_uint16), ("type", C.c_uint16), ("dns_class", C.c_uint16),
+                ("data_len", C.c_uint16), ("data_offset", C.c_uint16), ("section", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class DnsOut(C.Structure):
+    """pcppx_dns_out: the messages, the resource records, the names back to back, the disposition and the totals."""
+    _fields_ = [("msgs", C.c_void_p), ("rrs", C.c_void_p), ("names", C.c_void_p), ("names_cap", C.c_uint64),
+                ("disposition", C.c_void_p), ("max_msgs", C.c_uint32), ("max_rrs", C.c_uint32),
+                ("totals", C.c_void_p)]
+
+
+def make_dns_spec(sections: int = 15, max_msgs: int = 0) -> DnsSpec:
+    """sections: bit 0 queries, 1 answers, 2 authorities, 3 additionals."""
+    return DnsSpec(max_msgs, sections)
+
+
+def dns_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(DNS_FIELDS)}
+
+
+def dns_reference(batch: Batch, records: Records, max_layers: int, spec: DnsSpec, out: DnsOut) -> None:
+    """pcppx_dns_reference: pcppx_dns_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_dns_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                            C.byref(out)), "pcppx_dns_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -614,6 +677,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_tlsfp_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(TlsfpSpec),
                                           C.POINTER(Tlsfps)]
     lib.pcppx_tlsfp_reference.restype = C.c_int
+    lib.pcppx_dns_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(DnsSpec),
+                                     C.POINTER(DnsOut), P]
+    lib.pcppx_dns_device.restype = C.c_int
+    lib.pcppx_dns_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(DnsSpec),
+                                        C.POINTER(DnsOut)]
+    lib.pcppx_dns_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -642,6 +711,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
     "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_frag_device", "pcppx_frag_reference",
     "pcppx_tcpstream_device", "pcppx_tcpstream_reference", "pcppx_tlsfp_device", "pcppx_tlsfp_reference",
+    "pcppx_dns_device", "pcppx_dns_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

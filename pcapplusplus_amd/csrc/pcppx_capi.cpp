@@ -20,6 +20,7 @@
 #include "pcppx.h"
 #include "pcppx_internal.h"
 #include "pcppx_tlsfp.h"
+#include "pcppx_dns.h"
 
 namespace
 {
@@ -250,6 +251,8 @@ struct pcppx_ctx
 	Scratch frag;
 	// pcppx_tlsfp_device: the per-packet plans and the block sums and bases (tlsfp_scratch_bytes)
 	Scratch tlsfp;
+	// pcppx_dns_device: the per-packet plans and the block sums and bases (dns_scratch_bytes)
+	Scratch dns;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -932,6 +935,8 @@ extern "C"
 		c->frag.release(c->stream);
 		c->tlsfp.wait();
 		c->tlsfp.release(c->stream);
+		c->dns.wait();
+		c->dns.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -943,7 +948,7 @@ extern "C"
 			(void)hipHostFree(c->h_win);
 		}
 		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag,
-		                         &c->tlsfp })
+		                         &c->tlsfp, &c->dns })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1757,6 +1762,32 @@ extern "C"
 		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
 		rc = pcppx::launch_tlsfp(b, r->layers, max_layers, rec0, stride, s, o, c->tlsfp.ptr, st);
 		return rc != PCPPX_OK ? rc : c->tlsfp.mark_used(st);
+	}
+}
+
+// ---- dns: DnsLayer's resource records of the DNS packets of a batch (include/pcppx.h, dns) ----
+// pcppx_dns_reference is pcppx_dns_ref.cpp (plain C++); the argument rules both calls share are pcppx_dns.h's
+extern "C"
+{
+	int pcppx_dns_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                     const pcppx_dns_spec* s, pcppx_dns_out* o, void* hip_stream)
+	{
+		if (c == nullptr || !pcppx::dns::valid_args(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_DNS_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous dns call (possibly queued on another stream) owns the plans until it is done
+		int rc = c->dns.acquire(st, pcppx::dns_scratch_bytes(b->n));
+		if (rc != PCPPX_OK)
+			return rc;
+		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+		                                            : reinterpret_cast<const uint8_t*>(r->brief);
+		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+		rc = pcppx::launch_dns(b, r->layers, max_layers, rec0, stride, s, o, c->dns.ptr, st);
+		return rc != PCPPX_OK ? rc : c->dns.mark_used(st);
 	}
 }
 

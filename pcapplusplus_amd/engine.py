@@ -267,6 +267,25 @@ class Engine:
         abi.check(self.lib.pcppx_tlsfp_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                               C.byref(out), C.c_void_p(stream or 0)), "pcppx_tlsfp_device")
 
+    def dns_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.DnsSpec,
+                   msgs, rrs, totals, max_msgs: int, max_rrs: int, names=None, names_cap: int = 0, disposition=None,
+                   stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_dns_device over device tensors: one message (abi.DNS_MSG_DTYPE, 40 bytes) per DNS packet and one
+        record (abi.DNS_RR_DTYPE, 32 bytes) per linked resource of the sections spec asks for, with its decoded name.
+        summary (n * 32 bytes) or brief (n * 16 bytes): the parse's records, one of them; layers: FIXED,
+        n * max_layers * 8 bytes. msgs: max_msgs * 40 bytes; rrs: max_rrs * 32 bytes; names (u8, names_cap bytes; None =
+        no text); disposition (u8[n], optional); totals: 8 x i64 (abi.DNS_*), overwritten. All or nothing: on overflow
+        only the totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.DnsOut(abi.ptr(msgs), abi.ptr(rrs), opt(names), names_cap, opt(disposition), max_msgs, max_rrs,
+                         abi.ptr(totals))
+        abi.check(self.lib.pcppx_dns_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                            C.byref(out), C.c_void_p(stream or 0)), "pcppx_dns_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -824,6 +843,44 @@ def tlsfp_on_device(eng: Engine, batch: PacketBatch, client: bool = True, server
     assert tot["overflow"] == 0
     return (recs.cpu().numpy().view(abi.TLSFP_REC_DTYPE)[:k], text[:nb].cpu().numpy() if want_text else
             np.zeros(0, np.uint8), tuples.cpu().numpy().view(abi.TUPLE_DTYPE)[:n], disp[:n].cpu().numpy(), tot)
+
+
+def dns_on_device(eng: Engine, batch: PacketBatch, sections: int = 15, opts: abi.Opts | None = None,
+                  want_names: bool = True, device: str = "cuda:0"):
+    """Copy a host batch to HBM, parse it there and walk its DNS messages (pcppx_dns_device) without the records leaving
+    the device in between; copy the result back: (msgs abi.DNS_MSG_DTYPE[m] in source order, rrs abi.DNS_RR_DTYPE[k]
+    message by message, names u8 = the decoded names back to back (empty with want_names = False), disposition u8[n] =
+    abi.DNS_* per source packet, totals dict). The buffers are sized by a first call without room, which overflows and
+    writes the totals alone."""
+    import torch
+
+    opts = opts or abi.make_opts()
+    n, ml = batch.n, opts.max_layers
+    data, offsets, caplens = to_device(batch, device)
+    summary = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=device)
+    layers = torch.zeros(max(n * ml, 1) * 8, dtype=torch.uint8, device=device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, st)
+    spec = abi.make_dns_spec(sections)
+    totals = torch.empty(abi.DNS_TOTALS, dtype=torch.int64, device=device)
+
+    def call(msgs, max_msgs, rrs, max_rrs, names=None, cap=0, disp=None):
+        eng.dns_device(data, offsets, caplens, n, batch.linktype, layers, ml, spec, msgs, rrs, totals, max_msgs,
+                       max_rrs, names, cap, disp, st, summary=summary)
+        torch.cuda.synchronize(device)
+        return abi.dns_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    one = torch.empty(40, dtype=torch.uint8, device=device)
+    need = call(one, 0, one, 0)
+    m, k, nb = need["msgs"], need["rrs"], need["name_bytes"]
+    msgs = torch.empty(max(m, 1) * 40, dtype=torch.uint8, device=device)
+    rrs = torch.empty(max(k, 1) * 32, dtype=torch.uint8, device=device)
+    names = torch.empty(max(nb, 1), dtype=torch.uint8, device=device) if want_names else None
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(msgs, m, rrs, k, names, nb, disp)
+    assert tot["overflow"] == 0
+    return (msgs.cpu().numpy().view(abi.DNS_MSG_DTYPE)[:m], rrs.cpu().numpy().view(abi.DNS_RR_DTYPE)[:k],
+            names[:nb].cpu().numpy() if want_names else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
