@@ -1198,6 +1198,200 @@ PCPPX_API int pcppx_dns_device(pcppx_ctx* ctx, const pcppx_batch* batch, const p
 PCPPX_API int pcppx_dns_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                   const pcppx_dns_spec* spec, pcppx_dns_out* out);
 
+/* ---- http: the first line and the header fields of the HTTP packets of a device batch ----
+ * What HttpRequestFirstLine / HttpResponseFirstLine and TextBasedProtocolMessage::parseFields build
+ * (Packet++/src/HttpLayer.cpp:166-320, :850-985, TextBasedProtocol.cpp:87-139, :448-541), for packets that sit in HBM:
+ * per HTTP packet one message record (method, URI or status, version, header length, field count, content length),
+ * per header field the caller asked for one record, and the bytes it asked for back to back. It is what
+ * Examples/HttpAnalyzer reads of a packet (the method, the URI, getFieldByName("Host"), the status code,
+ * Content-Length, Content-Type, the header size). Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * Inputs: as dns. A device batch and its FIXED records (max_layers >= 1, the same value as the parse used; the summary
+ * or, when it is NULL, the brief supplies flags and n_layers; PACKED and DENSE records are refused).
+ *
+ * Per packet i the first rule that applies decides. Positions count from the layer's first byte; d[x] is the byte
+ * at x:
+ *   1 BAD_DESC. offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (the rule of select, steer, defrag, frag,
+ *     tlsfp and dns): the packet is never read.
+ *   2 The HTTP layer: the first entry k < min(n_layers, max_layers) with proto == 6 (pcpp::HTTPRequest) or 7
+ *     (HTTPResponse). It is followed only when it lies inside the packet (hdr_len <= data_len and offset + data_len <=
+ *     caplen); otherwise the packet is NONE and no later entry is looked at. L = data_len (m_DataLen), kind =
+ *     proto - 6. A kind that is not in spec->kinds makes the packet NONE.
+ *   3 No such entry: HOST when the host's chain may hold an HTTP layer the device did not record -- flags has
+ *     PCPPX_F_NEEDS_HOST_PROTO, OVERSIZE, BAD_DESC or DEPTH_OVERFLOW, or n_layers > max_layers, or NEEDS_HOST_L7 is set
+ *     with L7_HTTP set or without L7_KNOWN. Otherwise NONE.
+ *   4 A request's first line (HttpLayer.cpp:166-213, parseMethod :261-285, parseVersion :287-320, getUri :361-370).
+ *     The method is the text before the first space, looked up among GET HEAD POST PUT DELETE TRACE OPTIONS CONNECT
+ *     PATCH; it needs L >= 4 and the space at 1..L-1, and is 9 (unknown) otherwise. An unknown method gives
+ *     first_line_len = L, version 3, no URI, not complete. Otherwise u = len(method) + 1 and v is the first " HTTP/"
+ *     in [u, L). With no v, or v + 9 > L: version 3, no URI, first_line_len = L, not complete. Otherwise the version
+ *     comes from d[v+6..v+8] ("0.9", "1.0", "1.1", else 3) and the URI is [u, v); with e the first '\n' in [v + 6, L)
+ *     the line is complete with first_line_len = e + 1, and with no e it is L and not complete.
+ *   5 A response's first line (parseStatusCode :850-895, the constructor :897-929, parseVersion :964-985). The version
+ *     is known when L >= 8, the layer starts with "HTTP/" and d[5..7] is one of the three texts. status_code is the
+ *     number in d[9..11] when the version is known, L >= 12, the three bytes are digits, a '\n' exists in [13, L) and
+ *     the bytes between 13 and that '\n', less one trailing '\r', are not empty: those bytes are the status message.
+ *     Otherwise status_code is 0 and there is no message. No code table is consulted: a layer the parse recorded
+ *     always has a supported code. first_line_len is one past the first '\n' in [0, L), else L; complete means that
+ *     '\n' exists.
+ *   6 A field at off (HeaderField, TextBasedProtocol.cpp:448-541), e the first '\n' in [off, L): size = e - off + 1;
+ *     with no e, size is the bytes up to the first NUL or to L (:455-461). It is an end-of-header field when size == 0
+ *     or d[off] is '\r' or '\n' (:463-470). Otherwise c is the first ':' in [off, L) -- the whole remainder, not the
+ *     line (:475-477). With no c, or e exists and c >= e: name_len = size (the line end included) and no value
+ *     (:479-484). Otherwise name_len = c - off and vp = c + 1; vp moves over bytes ' ' while vp < L; vp >= L before or
+ *     after the skip means no value (:487-520); otherwise the value starts at vp and its length is L - vp with no e,
+ *     else e - vp, less one when d[e-1] == '\r' (:521-538). With no '\n' the colon may lie behind the NUL that ended
+ *     the field, so name_len can exceed size: that is kept.
+ *   7 The walk (parseFields :87-139, getFieldCount :355-361, isHeaderComplete :412-426, getHeaderLen :436-439). The
+ *     first field is at first_line_len and is linked always, at first_line_len == L too, where its size is 0. While
+ *     the current field is not end-of-header and off + size < L: the field at off + size is read, and linked when its
+ *     size is above 0; otherwise the walk ends. header_len is the last linked field's off + size; n_fields counts the
+ *     linked fields that are not end-of-header; HEADER_COMPLETE is set when the last linked field is end-of-header or
+ *     its name_len is 0 (isHeaderComplete compares getFieldName() with ""). The walk is linear in L: the position of
+ *     the next ':' is carried from field to field and searched again only once it lies behind the new field's start.
+ *   8 Names (:104-106, getFieldByName :395-410). A field's name bytes with 'A'..'Z' lowered, nothing else changed, are
+ *     compared with spec->names[k] byte for byte; a trailing space before the colon is part of the name. FIRST is set
+ *     on the first field of the message, in walk order, with a given name_id: the one getFieldByName returns. Records
+ *     are emitted for no field, for the fields with a name_id, or for all non-end fields, by spec->fields.
+ *   9 content_length, for both kinds (HttpLayer.cpp:728-737): the first non-end field whose lowered name is
+ *     "content-length", whatever names[] holds. HAS_CONTENT_LENGTH is set when it exists. The number is atoi of its
+ *     value cut at its first NUL, or of the empty text when it has no value: bytes of " \t\n\v\f\r" are skipped, then
+ *     one optional sign, then digits. When the magnitude exceeds 2^31 - 1, CONTENT_LENGTH_RANGE is set and the number
+ *     is 0 (atoi is undefined there).
+ *  10 Text. A message's text is its `a` bytes (the URI / the status message) when spec->text bit 0 is set, then the
+ *     value bytes of each emitted field that has a name_id and a value when bit 1 is set. text_len <= L, since the
+ *     ranges are disjoint.
+ *  11 Source bytes are read only inside [layer_offset, layer_offset + L) of in-bounds packets. */
+#define PCPPX_HTTP_MAX_NAMES 8
+#define PCPPX_HTTP_NAME_MAX 32
+
+typedef struct pcppx_http_spec { /* 272 bytes */
+	uint32_t max_msgs;  /* the HTTP packets the call has room for; 0 = n (always enough) */
+	uint8_t kinds;      /* bit 0 requests, bit 1 responses; 1..3 */
+	uint8_t fields;     /* PCPPX_HTTP_FIELDS_NONE (messages only), _WANTED (fields whose name is in names[]), _ALL */
+	uint8_t text;       /* bit 0 PCPPX_HTTP_TEXT_FIRST_LINE (the URI / the status message), bit 1 PCPPX_HTTP_TEXT_VALUES
+	                       (the values of wanted fields) */
+	uint8_t n_names;    /* 0..8 */
+	uint8_t name_len[PCPPX_HTTP_MAX_NAMES]; /* 1..32 for k < n_names, 0 beyond */
+	char names[PCPPX_HTTP_MAX_NAMES][PCPPX_HTTP_NAME_MAX]; /* lower case already: no byte 'A'..'Z'; no two equal;
+	                                                          unused bytes 0 */
+} pcppx_http_spec;
+
+#define PCPPX_HTTP_KIND_REQUESTS 1 /* pcppx_http_spec.kinds */
+#define PCPPX_HTTP_KIND_RESPONSES 2
+#define PCPPX_HTTP_FIELDS_NONE 0 /* pcppx_http_spec.fields */
+#define PCPPX_HTTP_FIELDS_WANTED 1
+#define PCPPX_HTTP_FIELDS_ALL 2
+#define PCPPX_HTTP_TEXT_FIRST_LINE 1 /* pcppx_http_spec.text */
+#define PCPPX_HTTP_TEXT_VALUES 2
+
+#define PCPPX_HTTP_REQUEST 0 /* pcppx_http_msg.kind */
+#define PCPPX_HTTP_RESPONSE 1
+#define PCPPX_HTTP_METHOD_UNKNOWN 9  /* pcppx_http_msg.method: HttpMethod 0..8 (GET HEAD POST PUT DELETE TRACE OPTIONS
+                                        CONNECT PATCH), else this */
+#define PCPPX_HTTP_VERSION_UNKNOWN 3 /* pcppx_http_msg.version: HttpVersion 0 "0.9", 1 "1.0", 2 "1.1", else this */
+
+/* pcppx_http_msg.flags */
+#define PCPPX_HTTP_FIRST_LINE_COMPLETE 1   /* the first line's isComplete() */
+#define PCPPX_HTTP_HEADER_COMPLETE 2       /* isHeaderComplete() */
+#define PCPPX_HTTP_HAS_CONTENT_LENGTH 4    /* getFieldByName("content-length") finds a field */
+#define PCPPX_HTTP_CONTENT_LENGTH_RANGE 8  /* its number does not fit an int: content_length is 0 */
+
+/* pcppx_http_field.flags */
+#define PCPPX_HTTP_HAS_VALUE 1 /* the field has a value (possibly of 0 bytes) */
+#define PCPPX_HTTP_FIRST 2     /* getFieldByName(names[name_id]) returns this field */
+#define PCPPX_HTTP_NO_NAME 0xFF /* pcppx_http_field.name_id of a name that is not in names[] */
+
+typedef struct pcppx_http_msg { /* 48 bytes per HTTP packet, in source order */
+	uint64_t first_field;    /* record number in out->fields of its first field record */
+	uint64_t text_pos;       /* its first byte in out->text */
+	uint32_t index;          /* source packet number (strictly ascending) */
+	int32_t content_length;  /* getContentLength(), rule 9 */
+	uint16_t layer_offset;   /* the HTTP layer's first byte, from the packet's first byte */
+	uint16_t layer_len;      /* L */
+	uint16_t header_len;     /* getHeaderLen() */
+	uint16_t first_line_len; /* the first line's getSize() */
+	uint16_t n_fields;       /* getFieldCount(), whatever spec->fields says */
+	uint16_t n_rec;          /* the field records emitted for it */
+	uint16_t a_offset;       /* request: the URI; response: the status message; from the layer's first byte */
+	uint16_t a_len;          /* 0 with a_offset 0 when there is none */
+	uint16_t status_code;    /* response: the number of rule 5, 0 = unknown; request: 0 */
+	uint16_t text_len;       /* the bytes it put into out->text */
+	uint8_t kind;            /* PCPPX_HTTP_REQUEST / PCPPX_HTTP_RESPONSE */
+	uint8_t method;          /* request: HttpMethod 0..8 or 9; response: 9 */
+	uint8_t version;         /* HttpVersion 0..2 or 3 */
+	uint8_t flags;           /* PCPPX_HTTP_FIRST_LINE_COMPLETE | HEADER_COMPLETE | HAS_CONTENT_LENGTH | CONTENT_LENGTH_RANGE */
+} pcppx_http_msg;
+
+typedef struct pcppx_http_field { /* 24 bytes per emitted field, message by message, in walk order */
+	uint64_t text_pos;     /* where its value lies (or would lie) in out->text */
+	uint32_t msg;          /* its message's record number in out->msgs */
+	uint16_t name_offset;  /* from the layer's first byte */
+	uint16_t name_len;     /* getFieldName().size() */
+	uint16_t value_offset; /* 0 with value_len 0 when the field has no value */
+	uint16_t value_len;    /* getFieldValue().size() */
+	uint16_t text_len;     /* value_len when its value went into out->text, else 0 */
+	uint8_t name_id;       /* k with names[k] equal to the lower-cased name, else PCPPX_HTTP_NO_NAME */
+	uint8_t flags;         /* PCPPX_HTTP_HAS_VALUE | PCPPX_HTTP_FIRST */
+} pcppx_http_field;
+
+/* pcppx_http_out.disposition values */
+#define PCPPX_HTTP_NONE 0     /* no HTTP layer of a kind in spec->kinds that is followed (in bounds) */
+#define PCPPX_HTTP_MSG 1      /* a message record */
+#define PCPPX_HTTP_HOST 2     /* no recorded HTTP layer, but the host's chain may hold one (rule 3) */
+#define PCPPX_HTTP_BAD_DESC 3 /* the descriptor is out of bounds: never read */
+
+/* pcppx_http_out.totals words */
+#define PCPPX_HTTP_MSGS 0
+#define PCPPX_HTTP_REQUESTS 1
+#define PCPPX_HTTP_RESPONSES 2
+#define PCPPX_HTTP_FIELDS 3        /* the field records emitted */
+#define PCPPX_HTTP_TEXT_BYTES 4
+#define PCPPX_HTTP_HOST_N 5
+#define PCPPX_HTTP_BAD_DESC_N 6
+#define PCPPX_HTTP_HEADER_BYTES 7  /* the sum of header_len: HttpAnalyzer's totalMessageHeaderSize */
+#define PCPPX_HTTP_FIELDS_LINKED 8 /* the sum of n_fields */
+/* words 9 and 10 are zero */
+#define PCPPX_HTTP_OVERFLOW 11
+#define PCPPX_HTTP_TOTALS 12
+
+typedef struct pcppx_http_out { /* device pointers; host pointers for pcppx_http_reference */
+	pcppx_http_msg* msgs;     /* max_msgs entries, in source order */
+	pcppx_http_field* fields; /* max_fields entries: message by message, each in walk order */
+	uint8_t* text;            /* the messages' text back to back in record order, no terminator; NULL = no text */
+	uint64_t text_cap;
+	uint8_t* disposition;     /* optional (NULL): n entries, PCPPX_HTTP_* per source packet */
+	uint32_t max_msgs;
+	uint32_t max_fields;
+	uint64_t* totals;         /* PCPPX_HTTP_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_http_out;
+
+/* Capacity is all or nothing, as in dns: OVERFLOW = 1 iff MSGS > out->max_msgs, or FIELDS > max_fields, or text != NULL
+ * and TEXT_BYTES > text_cap, or MSGS > spec->max_msgs (0 = n). Then only the totals are written (no record, no byte of
+ * text, no disposition); they always hold the full would-be values. With text == NULL positions and lengths are still
+ * filled and the byte capacity is not applied. Sizing: a call with max_msgs = max_fields = 0 overflows and gives MSGS,
+ * FIELDS and TEXT_BYTES. The cost of a packet is linear in its layer's L bytes.
+ * Source bytes are read only from in-bounds packets, inside a recorded HTTP layer that lies inside the packet. Nothing
+ * is written outside the first MSGS messages, the first FIELDS records, [0, TEXT_BYTES) of text and the n dispositions.
+ * The output is a pure function of the inputs, bit-identical from run to run: positions come from counts and scans, and
+ * there are no atomics. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals, msgs or fields; with n > 0 a null
+ * records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS; kinds 0 or above 3; fields above 2; text above 3; n_names above 8; a name_len of 0 or above 32 for
+ * k < n_names, or not 0 beyond; a byte 'A'..'Z' in a name; two equal names. The work is queued on hip_stream and the
+ * call returns without waiting; calls on one context are ordered through its http scratch (a buffer and an event of
+ * their own, as dns's). Scratch: with g = ceil(n / 1024) blocks, 60 g + 16 n bytes (per block nine 32-bit sums -- its
+ * messages, field records, text bytes, requests, responses, HOST and BAD_DESC packets, header bytes and linked
+ * fields -- and the 64-bit exclusive prefixes of the first three; per packet a 16-byte plan: the layer's offset and
+ * length, the kind, the records and text bytes of the message, its header length and linked fields, and the
+ * disposition); PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_http_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                uint8_t max_layers, const pcppx_http_spec* spec, pcppx_http_out* out,
+                                void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_http_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                   const pcppx_http_spec* spec, pcppx_http_out* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

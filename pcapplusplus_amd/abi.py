@@ -447,6 +447,91 @@ def dns_reference(batch: Batch, records: Records, max_layers: int, spec: DnsSpec
                                             C.byref(out)), "pcppx_dns_reference")
 
 
+# pcppx_http_*: the first line and the header fields of the HTTP packets of a batch (include/pcppx.h, http)
+HTTP_NONE, HTTP_MSG, HTTP_HOST, HTTP_BAD_DESC = range(4)  # disposition
+HTTP_REQUEST, HTTP_RESPONSE = 0, 1                        # msg.kind
+HTTP_KIND_REQUESTS, HTTP_KIND_RESPONSES = 1, 2            # spec.kinds bits
+HTTP_FIELDS_NONE, HTTP_FIELDS_WANTED, HTTP_FIELDS_ALL = range(3)  # spec.fields
+HTTP_TEXT_FIRST_LINE, HTTP_TEXT_VALUES = 1, 2             # spec.text bits
+HTTP_METHODS = ("GET", "HEAD", "POST", "PUT", "DELETE", "TRACE", "OPTIONS", "CONNECT", "PATCH")  # msg.method 0..8
+HTTP_METHOD_UNKNOWN = 9
+HTTP_VERSIONS = ("0.9", "1.0", "1.1")                     # msg.version 0..2
+HTTP_VERSION_UNKNOWN = 3
+HTTP_FIRST_LINE_COMPLETE, HTTP_HEADER_COMPLETE, HTTP_HAS_CONTENT_LENGTH, HTTP_CONTENT_LENGTH_RANGE = 1, 2, 4, 8
+HTTP_HAS_VALUE, HTTP_FIRST = 1, 2                         # field.flags
+HTTP_NO_NAME = 0xFF
+HTTP_MAX_NAMES, HTTP_NAME_MAX = 8, 32
+(HTTP_MSGS, HTTP_REQUESTS, HTTP_RESPONSES, HTTP_FIELDS, HTTP_TEXT_BYTES, HTTP_HOST_N, HTTP_BAD_DESC_N,
+ HTTP_HEADER_BYTES, HTTP_FIELDS_LINKED, _HTTP_ZERO0, _HTTP_ZERO1, HTTP_OVERFLOW) = range(12)  # pcppx_http_out.totals
+HTTP_TOTALS = 12
+HTTP_TOTAL_NAMES = ("msgs", "requests", "responses", "fields", "text_bytes", "host_n", "bad_desc", "header_bytes",
+                    "fields_linked", "zero0", "zero1", "overflow")
+HTTP_MSG_DTYPE = np.dtype(
+    [("first_field", "<u8"), ("text_pos", "<u8"), ("index", "<u4"), ("content_length", "<i4"), ("layer_offset", "<u2"),
+     ("layer_len", "<u2"), ("header_len", "<u2"), ("first_line_len", "<u2"), ("n_fields", "<u2"), ("n_rec", "<u2"),
+     ("a_offset", "<u2"), ("a_len", "<u2"), ("status_code", "<u2"), ("text_len", "<u2"), ("kind", "u1"),
+     ("method", "u1"), ("version", "u1"), ("flags", "u1")]
+)
+HTTP_FIELD_DTYPE = np.dtype(
+    [("text_pos", "<u8"), ("msg", "<u4"), ("name_offset", "<u2"), ("name_len", "<u2"), ("value_offset", "<u2"),
+     ("value_len", "<u2"), ("text_len", "<u2"), ("name_id", "u1"), ("flags", "u1")]
+)
+assert HTTP_MSG_DTYPE.itemsize == 48 and HTTP_FIELD_DTYPE.itemsize == 24
+
+
+class HttpSpec(C.Structure):
+    """pcppx_http_spec: the room for HTTP packets (0 = n), the kinds, which fields get records, which bytes go to the
+    text, and the wanted names in lower case."""
+    _fields_ = [("max_msgs", C.c_uint32), ("kinds", C.c_uint8), ("fields", C.c_uint8), ("text", C.c_uint8),
+                ("n_names", C.c_uint8), ("name_len", C.c_uint8 * 8), ("names", (C.c_char * 32) * 8)]
+
+
+class HttpMsg(C.Structure):
+    """pcppx_http_msg (HTTP_MSG_DTYPE is its numpy mirror)."""
+    _fields_ = [("first_field", C.c_uint64), ("text_pos", C.c_uint64), ("index", C.c_uint32),
+                ("content_length", C.c_int32), ("layer_offset", C.c_uint16), ("layer_len", C.c_uint16),
+                ("header_len", C.c_uint16), ("first_line_len", C.c_uint16), ("n_fields", C.c_uint16),
+                ("n_rec", C.c_uint16), ("a_offset", C.c_uint16), ("a_len", C.c_uint16), ("status_code", C.c_uint16),
+                ("text_len", C.c_uint16), ("kind", C.c_uint8), ("method", C.c_uint8), ("version", C.c_uint8),
+                ("flags", C.c_uint8)]
+
+
+class HttpField(C.Structure):
+    """pcppx_http_field (HTTP_FIELD_DTYPE is its numpy mirror)."""
+    _fields_ = [("text_pos", C.c_uint64), ("msg", C.c_uint32), ("name_offset", C.c_uint16), ("name_len", C.c_uint16),
+                ("value_offset", C.c_uint16), ("value_len", C.c_uint16), ("text_len", C.c_uint16),
+                ("name_id", C.c_uint8), ("flags", C.c_uint8)]
+
+
+class HttpOut(C.Structure):
+    """pcppx_http_out: the messages, the field records, the text back to back, the disposition and the totals."""
+    _fields_ = [("msgs", C.c_void_p), ("fields", C.c_void_p), ("text", C.c_void_p), ("text_cap", C.c_uint64),
+                ("disposition", C.c_void_p), ("max_msgs", C.c_uint32), ("max_fields", C.c_uint32),
+                ("totals", C.c_void_p)]
+
+
+def make_http_spec(names=(), fields: int = HTTP_FIELDS_WANTED, text: int = 3, kinds: int = 3,
+                   max_msgs: int = 0) -> HttpSpec:
+    """names: up to 8 field names of 1..32 bytes (str or bytes), lower case; the call refuses anything else."""
+    s = HttpSpec(max_msgs, kinds, fields, text, len(names))
+    for k, nm in enumerate(names[:HTTP_MAX_NAMES]):
+        raw = nm.encode("latin-1") if isinstance(nm, str) else bytes(nm)
+        s.name_len[k] = min(len(raw), 255)
+        C.memmove(C.addressof(s.names[k]), raw[:HTTP_NAME_MAX], min(len(raw), HTTP_NAME_MAX))
+    return s
+
+
+def http_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(HTTP_TOTAL_NAMES)}
+
+
+def http_reference(batch: Batch, records: Records, max_layers: int, spec: HttpSpec, out: HttpOut) -> None:
+    """pcppx_http_reference: pcppx_http_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_http_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                             C.byref(out)), "pcppx_http_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -683,6 +768,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_dns_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(DnsSpec),
                                         C.POINTER(DnsOut)]
     lib.pcppx_dns_reference.restype = C.c_int
+    lib.pcppx_http_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(HttpSpec),
+                                      C.POINTER(HttpOut), P]
+    lib.pcppx_http_device.restype = C.c_int
+    lib.pcppx_http_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(HttpSpec),
+                                         C.POINTER(HttpOut)]
+    lib.pcppx_http_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -712,6 +803,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_frag_device", "pcppx_frag_reference",
     "pcppx_tcpstream_device", "pcppx_tcpstream_reference", "pcppx_tlsfp_device", "pcppx_tlsfp_reference",
     "pcppx_dns_device", "pcppx_dns_reference",
+    "pcppx_http_device", "pcppx_http_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

@@ -21,6 +21,7 @@
 #include "pcppx_internal.h"
 #include "pcppx_tlsfp.h"
 #include "pcppx_dns.h"
+#include "pcppx_http.h"
 
 namespace
 {
@@ -253,6 +254,8 @@ struct pcppx_ctx
 	Scratch tlsfp;
 	// pcppx_dns_device: the per-packet plans and the block sums and bases (dns_scratch_bytes)
 	Scratch dns;
+	// pcppx_http_device: the per-packet plans and the block sums and bases (http_scratch_bytes)
+	Scratch http;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -937,6 +940,8 @@ extern "C"
 		c->tlsfp.release(c->stream);
 		c->dns.wait();
 		c->dns.release(c->stream);
+		c->http.wait();
+		c->http.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -948,7 +953,7 @@ extern "C"
 			(void)hipHostFree(c->h_win);
 		}
 		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag,
-		                         &c->tlsfp, &c->dns })
+		                         &c->tlsfp, &c->dns, &c->http })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1788,6 +1793,32 @@ extern "C"
 		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
 		rc = pcppx::launch_dns(b, r->layers, max_layers, rec0, stride, s, o, c->dns.ptr, st);
 		return rc != PCPPX_OK ? rc : c->dns.mark_used(st);
+	}
+}
+
+// ---- http: the first line and the header fields of the HTTP packets of a batch (include/pcppx.h, http) ----
+// pcppx_http_reference is pcppx_http_ref.cpp (plain C++); the argument rules both calls share are pcppx_http.h's
+extern "C"
+{
+	int pcppx_http_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                      const pcppx_http_spec* s, pcppx_http_out* o, void* hip_stream)
+	{
+		if (c == nullptr || !pcppx::http::valid_args(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_HTTP_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous http call (possibly queued on another stream) owns the plans until it is done
+		int rc = c->http.acquire(st, pcppx::http_scratch_bytes(b->n));
+		if (rc != PCPPX_OK)
+			return rc;
+		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+		                                            : reinterpret_cast<const uint8_t*>(r->brief);
+		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+		rc = pcppx::launch_http(b, r->layers, max_layers, rec0, stride, s, o, c->http.ptr, st);
+		return rc != PCPPX_OK ? rc : c->http.mark_used(st);
 	}
 }
 

@@ -286,6 +286,26 @@ class Engine:
         abi.check(self.lib.pcppx_dns_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_dns_device")
 
+    def http_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.HttpSpec,
+                    msgs, fields, totals, max_msgs: int, max_fields: int, text=None, text_cap: int = 0,
+                    disposition=None, stream: int | None = None, data_len: int | None = None, summary=None,
+                    brief=None) -> None:
+        """Queue pcppx_http_device over device tensors: one message (abi.HTTP_MSG_DTYPE, 48 bytes) per HTTP packet and
+        one record (abi.HTTP_FIELD_DTYPE, 24 bytes) per header field spec asks for, with the bytes spec asks for.
+        summary (n * 32 bytes) or brief (n * 16 bytes): the parse's records, one of them; layers: FIXED,
+        n * max_layers * 8 bytes. msgs: max_msgs * 48 bytes; fields: max_fields * 24 bytes; text (u8, text_cap bytes;
+        None = no text); disposition (u8[n], optional); totals: 12 x i64 (abi.HTTP_*), overwritten. All or nothing: on
+        overflow only the totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.HttpOut(abi.ptr(msgs), abi.ptr(fields), opt(text), text_cap, opt(disposition), max_msgs, max_fields,
+                          abi.ptr(totals))
+        abi.check(self.lib.pcppx_http_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_http_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -881,6 +901,44 @@ def dns_on_device(eng: Engine, batch: PacketBatch, sections: int = 15, opts: abi
     assert tot["overflow"] == 0
     return (msgs.cpu().numpy().view(abi.DNS_MSG_DTYPE)[:m], rrs.cpu().numpy().view(abi.DNS_RR_DTYPE)[:k],
             names[:nb].cpu().numpy() if want_names else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
+
+
+def http_on_device(eng: Engine, batch: PacketBatch, spec: abi.HttpSpec | None = None, opts: abi.Opts | None = None,
+                   want_text: bool = True, device: str = "cuda:0"):
+    """Copy a host batch to HBM, parse it there and walk its HTTP messages (pcppx_http_device) without the records
+    leaving the device in between; copy the result back: (msgs abi.HTTP_MSG_DTYPE[m] in source order, fields
+    abi.HTTP_FIELD_DTYPE[k] message by message, text u8 = the bytes spec asks for back to back (empty with want_text =
+    False), disposition u8[n] = abi.HTTP_* per source packet, totals dict). spec None: every field, the first line's
+    text. The buffers are sized by a first call without room, which overflows and writes the totals alone."""
+    import torch
+
+    opts = opts or abi.make_opts()
+    spec = spec or abi.make_http_spec((), abi.HTTP_FIELDS_ALL, abi.HTTP_TEXT_FIRST_LINE)
+    n, ml = batch.n, opts.max_layers
+    data, offsets, caplens = to_device(batch, device)
+    summary = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=device)
+    layers = torch.zeros(max(n * ml, 1) * 8, dtype=torch.uint8, device=device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, st)
+    totals = torch.empty(abi.HTTP_TOTALS, dtype=torch.int64, device=device)
+
+    def call(msgs, max_msgs, fields, max_fields, text=None, cap=0, disp=None):
+        eng.http_device(data, offsets, caplens, n, batch.linktype, layers, ml, spec, msgs, fields, totals, max_msgs,
+                        max_fields, text, cap, disp, st, summary=summary)
+        torch.cuda.synchronize(device)
+        return abi.http_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    one = torch.empty(48, dtype=torch.uint8, device=device)
+    need = call(one, 0, one, 0)
+    m, k, nb = need["msgs"], need["fields"], need["text_bytes"]
+    msgs = torch.empty(max(m, 1) * 48, dtype=torch.uint8, device=device)
+    fields = torch.empty(max(k, 1) * 24, dtype=torch.uint8, device=device)
+    text = torch.empty(max(nb, 1), dtype=torch.uint8, device=device) if want_text else None
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(msgs, m, fields, k, text, nb, disp)
+    assert tot["overflow"] == 0
+    return (msgs.cpu().numpy().view(abi.HTTP_MSG_DTYPE)[:m], fields.cpu().numpy().view(abi.HTTP_FIELD_DTYPE)[:k],
+            text[:nb].cpu().numpy() if want_text else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
