@@ -588,8 +588,8 @@ typedef struct pcppx_defrag_spec {
 
 /* pcppx_defragged.disposition values */
 #define PCPPX_DEFRAG_PASS 0        /* not an IPv4 fragment (in bounds) */
-#define PCPPX_DEFRAG_LEFT 1        /* an IPv4 fragment of a group the device did not reassemble, or an IPv6 fragment:
-                                      the host table decides */
+#define PCPPX_DEFRAG_LEFT 1        /* an IPv4 fragment of a group the device did not reassemble, or an IPv6 fragment,
+                                      or a fragment of a family the spec does not ask for: the host table decides */
 #define PCPPX_DEFRAG_MERGED 2      /* merged into a reassembled packet */
 #define PCPPX_DEFRAG_MERGED_LAST 3 /* merged, and its output slot holds the packet */
 #define PCPPX_DEFRAG_BAD_DESC 4    /* the descriptor is out of bounds: never read, never copied */
@@ -651,6 +651,75 @@ PCPPX_API int pcppx_defrag_device(pcppx_ctx* ctx, const pcppx_batch* batch, cons
 /* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
 PCPPX_API int pcppx_defrag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                      const pcppx_reasm_info* info, const pcppx_defrag_spec* spec, pcppx_defragged* out);
+
+/* ---- defrag6: defrag for both families: the IPv6 fragment groups of a device batch are reassembled too ----
+ * IPReassembly::processPacket keeps the fragments of IPv4 and IPv6 in one table and Examples/IPDefragUtil counts both;
+ * pcppx_defrag_device leaves every IPv6 fragment to the host. This call takes the families the spec names. Everything
+ * not said here is pcppx_defrag_device's contract: the inputs, pcppx_defragged, the dispositions and totals words, the
+ * output order, passthrough, the all-or-nothing capacity rule, the 16-B granule rule, determinism, n == 0, the scratch
+ * formula, the stream ordering (the two calls share one scratch buffer and event per context) and the batch-local
+ * caveat. Added within ABI 7: new symbols only. With families = PCPPX_DEFRAG_FAM_V4 every output column and every
+ * byte equals pcppx_defrag_device's (the same kernels run).
+ *
+ * Candidates. An IPv4 fragment (PCPPX_IPR_F_IPV6 not set) is a candidate by defrag's rule. With families other than
+ * PCPPX_DEFRAG_FAM_V4 alone, packet i is an IPv6 candidate iff (info[i].ip_status & 15) == PCPPX_IPR_FRAGMENT,
+ * PCPPX_IPR_F_IPV6 is set, its descriptor is in bounds and its chain records an IPv6 layer: the first layer of protocol
+ * IPv6 among the first min(n_layers, max_layers) entries, the one IPv6FragmentWrapper takes (IPReassembly.cpp:147).
+ * Then ip_off = layer.offset, hdr = layer.hdr_len (the fixed header and every extension parseExtensions walked:
+ * hdr >= 48, one fragment header at least) and len = layer.data_len - hdr (getIPLayerPayloadSize()). The layer must lie
+ * inside the packet (hdr <= data_len, offset + data_len <= caplen), as in defrag. len comes from the records, not from
+ * the payload-length field: the reference's constructor clamps the layer to payloadLength + getHeaderLen()
+ * (IPv6Layer.cpp:37-39), which counts the extension bytes twice, so up to hdr - 40 bytes of a trailer count as payload
+ * there, and in the parse's data_len too. A group with such a member fails the tiling rule below and is LEFT, as it
+ * must be: the reference takes its duplicate path.
+ *
+ * Families. With families = V4 an IPv6 fragment is LEFT and never enters a group: today's result. With families = V6
+ * or V4 | V6 the candidates of both families form the groups, by ip_key alone as m_FragmentMap does
+ * (IPReassembly.cpp:322-327), and CANDIDATES counts both. A group is clean only if all of its members are of one
+ * family and the spec asks for that family: two families that collide in the 32-bit key are never appended to one
+ * another, and with families = V6 an IPv4 candidate is LEFT and so is every IPv6 fragment it shares its key with (an
+ * IPv4 FRAGMENT packet that is no candidate -- no IPv4 layer recorded -- joins no group under any spec).
+ *
+ * Clean groups: defrag's rule, word for word (2..PCPPX_DEFRAG_MAX_FRAGS members, every len > 0, an exact tiling from 0
+ * by (frag_offset, source index), PCPPX_IPR_F_LAST on the sorted-last member only), with the same two bounds on the
+ * first member's ip_off and hdr: ip_off + hdr + total <= PCPPX_MAX_CAPLEN (the intermediate packet of :364-372 and
+ * :411 still holds the extensions) and hdr + total <= 65535 (the 16-bit store of :476). processPacket runs the same
+ * lines for both families, so defrag's argument that the result does not depend on the order of arrival carries over.
+ * One condition is added, on the first member of an IPv6 group: its extension chain, walked as parseExtensions does
+ * (IPv6Layer.cpp:79-147) from the fixed header's next-header byte over [ip_off + 40, ip_off + hdr) -- types 0, 43 and
+ * 60 are (len8 + 1) * 8 bytes long, type 44 is 8, type 51 is (len8 + 2) * 4 -- must end exactly at hdr, must hold a
+ * fragment header (it need not be the last extension), and the last extension's next-header byte nh must not itself
+ * be one of these five types: the parse of the longer, reassembled packet (:481) would walk on into the payload and
+ * removeAllExtensions would cut more than hdr - 40 bytes. The walk takes at most (hdr - 40) / 8 steps and reads
+ * nothing outside the packet. A chain that fails is one the records do not describe: the group is LEFT.
+ *
+ * The reassembled IPv6 packet (IPReassembly.cpp:472-496; IPv6Layer.cpp:179-187, 314-356), with T = total and
+ * H = hdr: bytes [0, ip_off + 40) of the first member, then the payloads of all members in offset order from
+ * ip_off + 40 on. removeAllExtensions cuts every extension of the first member, a Hop-by-Hop header ahead of the
+ * fragment header too; the first member's trailer is dropped. Its length is ip_off + 40 + T. In the IPv6 header at
+ * ip_off, byte 6 = nh and bytes 4-5 = be16(min(T, bswap16(T + H))): line 476 stores T + H without htobe16, the parse
+ * of :481 clamps the layer to that byte-swapped value plus H (IPv6Layer.cpp:37-39), and computeCalculateFields writes
+ * the clamped length minus the fixed header back. (T = 1488, H = 48: T + H = 0x0600, the field says 6 and the packet
+ * is 1488 bytes behind its fixed header all the same; T = 1192: 1192.) A parse of the output sees what the
+ * reference's caller sees. Nothing else changes: there is no checksum, and computeCalculateFields rewrites the
+ * next-header byte only to the value parseNextLayer dispatched on. first / frags / index are as in defrag.
+ *
+ * PCPPX_E_INVAL before any device work: defrag's list, and families 0 or with a bit above PCPPX_DEFRAG_FAM_V6. */
+#define PCPPX_DEFRAG_FAM_V4 1
+#define PCPPX_DEFRAG_FAM_V6 2
+typedef struct pcppx_defrag6_spec {
+	uint32_t max_fragments; /* the candidates the call has room for; 0 = n (always enough) */
+	uint8_t passthrough;    /* 0 / 1 */
+	uint8_t families;       /* PCPPX_DEFRAG_FAM_* bits; 0 or bits above 3: PCPPX_E_INVAL */
+	uint8_t reserved[2];    /* 0 */
+} pcppx_defrag6_spec;
+PCPPX_API int pcppx_defrag6_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                   uint8_t max_layers, const pcppx_reasm_info* info, const pcppx_defrag6_spec* spec,
+                                   pcppx_defragged* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_defrag6_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                      const pcppx_reasm_info* info, const pcppx_defrag6_spec* spec,
+                                      pcppx_defragged* out);
 
 /* ---- tcpstream: reassemble the TCP connection sides that are clean inside one device batch (TcpReassembly) ----
  * pcppx_reasm_device stops at the connection table; this is the table's common case, for packets that sit in HBM:

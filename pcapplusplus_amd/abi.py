@@ -256,6 +256,28 @@ def defrag_reference(batch: Batch, records: Records, max_layers: int, info, spec
                                                C.byref(out)), "pcppx_defrag_reference")
 
 
+# pcppx_defrag6_*: defrag for both families (include/pcppx.h, defrag6)
+DEFRAG_FAM_V4, DEFRAG_FAM_V6 = 1, 2
+
+
+class Defrag6Spec(C.Structure):
+    """pcppx_defrag6_spec: pcppx_defrag_spec and the families (DEFRAG_FAM_* bits) whose groups are reassembled."""
+    _fields_ = [("max_fragments", C.c_uint32), ("passthrough", C.c_uint8), ("families", C.c_uint8),
+                ("reserved", C.c_uint8 * 2)]
+
+
+def make_defrag6_spec(passthrough: bool = True, max_fragments: int = 0,
+                      families: int = DEFRAG_FAM_V4 | DEFRAG_FAM_V6) -> Defrag6Spec:
+    return Defrag6Spec(max_fragments, 1 if passthrough else 0, families)
+
+
+def defrag6_reference(batch: Batch, records: Records, max_layers: int, info, spec: Defrag6Spec, out: Defragged) -> None:
+    """pcppx_defrag6_reference: pcppx_defrag6_device's contract in plain C++ over host pointers (no GPU); the
+    arguments are defrag_reference's."""
+    check(load_engine().pcppx_defrag6_reference(C.byref(batch), C.byref(records), max_layers, info, C.byref(spec),
+                                                C.byref(out)), "pcppx_defrag6_reference")
+
+
 # pcppx_tcpstream_*: the TCP connection sides that are clean inside a batch (include/pcppx.h, tcpstream)
 TCPS_F_SYN, TCPS_F_FIN, TCPS_F_RST, TCPS_F_OOO = 1, 2, 4, 8  # pcppx_tcpstream_rec.flags
 TCPS_NOT_TCP, TCPS_HOST, TCPS_LEFT, TCPS_STREAM, TCPS_CONTROL, TCPS_BAD_DESC = range(6)  # disposition values
@@ -744,6 +766,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_defrag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P, C.POINTER(DefragSpec),
                                            C.POINTER(Defragged)]
     lib.pcppx_defrag_reference.restype = C.c_int
+    lib.pcppx_defrag6_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P,
+                                         C.POINTER(Defrag6Spec), C.POINTER(Defragged), P]
+    lib.pcppx_defrag6_device.restype = C.c_int
+    lib.pcppx_defrag6_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P,
+                                            C.POINTER(Defrag6Spec), C.POINTER(Defragged)]
+    lib.pcppx_defrag6_reference.restype = C.c_int
     lib.pcppx_tcpstream_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, P,
                                            C.POINTER(TcpStreamSpec), C.POINTER(TcpStreams), P]
     lib.pcppx_tcpstream_device.restype = C.c_int
@@ -800,7 +828,8 @@ EXPORTED_SYMBOLS = (
     "pcppx_pcap_read_batch", "pcppx_pcap_read_batch_ex", "pcppx_pcap_map_batch", "pcppx_pcap_close", "pcppx_host_alloc", "pcppx_host_free",
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
-    "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_frag_device", "pcppx_frag_reference",
+    "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_defrag6_device", "pcppx_defrag6_reference",
+    "pcppx_frag_device", "pcppx_frag_reference",
     "pcppx_tcpstream_device", "pcppx_tcpstream_reference", "pcppx_tlsfp_device", "pcppx_tlsfp_reference",
     "pcppx_dns_device", "pcppx_dns_reference",
     "pcppx_http_device", "pcppx_http_reference",

@@ -1477,23 +1477,50 @@ extern "C"
 	}
 }
 
-// ---- defrag: the IPv4 fragment groups that are complete inside a batch (include/pcppx.h, defrag) ----
+// ---- defrag: the IPv4 / IPv6 fragment groups that are complete inside a batch (include/pcppx.h, defrag, defrag6) ----
 namespace
 {
-// the argument rules pcppx_defrag_device and pcppx_defrag_reference share (include/pcppx.h)
-bool valid_defrag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
-                  const pcppx_defrag_spec* s, const pcppx_defragged* o)
+// a spec of either entry point: pcppx_defrag_spec is families = V4
+struct DefragRules
 {
-	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
+	uint32_t max_fragments, passthrough, families;
+};
+
+// the argument rules the four defrag calls share but for the spec's own fields (include/pcppx.h)
+bool valid_defrag_args(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
+                       const pcppx_defragged* o)
+{
+	if (b == nullptr || r == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
 	    o->caplens == nullptr)
 		return false;
 	if (max_layers == 0 || max_layers > PCPPX_MAX_LAYERS || r->layout != PCPPX_LAYOUT_FIXED)
 		return false;
-	if (s->passthrough > 1 || s->reserved[0] != 0 || s->reserved[1] != 0 || s->reserved[2] != 0 || o->reserved != 0)
+	if (o->reserved != 0)
 		return false;
 	if (b->n != 0 && (info == nullptr || r->layers == nullptr || (r->summary == nullptr && r->brief == nullptr)))
 		return false;
 	return valid_batch(b);
+}
+
+// the argument rules pcppx_defrag_device and pcppx_defrag_reference share
+bool valid_defrag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
+                  const pcppx_defrag_spec* s, const pcppx_defragged* o, DefragRules& rules)
+{
+	if (s == nullptr || s->passthrough > 1 || s->reserved[0] != 0 || s->reserved[1] != 0 || s->reserved[2] != 0)
+		return false;
+	rules = { s->max_fragments, s->passthrough, PCPPX_DEFRAG_FAM_V4 };
+	return valid_defrag_args(b, r, max_layers, info, o);
+}
+
+// and the ones pcppx_defrag6_device and pcppx_defrag6_reference share
+bool valid_defrag6(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
+                   const pcppx_defrag6_spec* s, const pcppx_defragged* o, DefragRules& rules)
+{
+	if (s == nullptr || s->passthrough > 1 || s->reserved[0] != 0 || s->reserved[1] != 0 || s->families == 0 ||
+	    s->families > (PCPPX_DEFRAG_FAM_V4 | PCPPX_DEFRAG_FAM_V6))
+		return false;
+	rules = { s->max_fragments, s->passthrough, s->families };
+	return valid_defrag_args(b, r, max_layers, info, o);
 }
 
 // where the chain lengths are read from: the summary's n_layers, else the brief's
@@ -1507,175 +1534,217 @@ const uint8_t* n_layers_column(const pcppx_records* r, uint32_t& stride)
 	stride = sizeof(pcppx_brief);
 	return &r->brief->n_layers;
 }
-}  // namespace
 
-extern "C"
+// pcppx_defrag_device and pcppx_defrag6_device behind their argument checks
+int defrag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+                  const pcppx_reasm_info* info, const DefragRules& s, pcppx_defragged* o, void* hip_stream)
 {
-	int pcppx_defrag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
-	                        const pcppx_reasm_info* info, const pcppx_defrag_spec* s, pcppx_defragged* o,
-	                        void* hip_stream)
-	{
-		if (c == nullptr || !valid_defrag(b, r, max_layers, info, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_DEFRAG_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous defrag (possibly queued on another stream) owns the table until it is done
-		int rc = c->defrag.acquire(st, pcppx::defrag_scratch_bytes(b->n, s->max_fragments));
-		if (rc != PCPPX_OK)
-			return rc;
-		uint32_t stride;
-		const uint8_t* nl = n_layers_column(r, stride);
-		rc = pcppx::launch_defrag(b, r->layers, max_layers, nl, stride, info, s, o, c->defrag.ptr, st);
-		return rc != PCPPX_OK ? rc : c->defrag.mark_used(st);
-	}
+	if (!ok(hipSetDevice(c->device)))
+		return PCPPX_E_HIP;
+	hipStream_t st = static_cast<hipStream_t>(hip_stream);
+	if (b->n == 0)
+		return ok(hipMemsetAsync(o->totals, 0, PCPPX_DEFRAG_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+	// the context's previous defrag (possibly queued on another stream) owns the table until it is done
+	int rc = c->defrag.acquire(st, pcppx::defrag_scratch_bytes(b->n, s.max_fragments));
+	if (rc != PCPPX_OK)
+		return rc;
+	uint32_t stride;
+	const uint8_t* nl = n_layers_column(r, stride);
+	rc = pcppx::launch_defrag(b, r->layers, max_layers, nl, stride, info, s.max_fragments, s.passthrough, s.families,
+	                          o, c->defrag.ptr, st);
+	return rc != PCPPX_OK ? rc : c->defrag.mark_used(st);
+}
 
-	int pcppx_defrag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
-	                           const pcppx_reasm_info* info, const pcppx_defrag_spec* s, pcppx_defragged* o)
+// the next-header values parseExtensions (IPv6Layer.cpp:79-147) takes for an extension
+bool is_v6_extension(uint32_t nh)
+{
+	return nh == 0 || nh == 43 || nh == 44 || nh == 51 || nh == 60;
+}
+
+// parseExtensions over the extensions ip[40, hdr) of an IPv6 header (hdr >= 48, inside the packet): true iff the chain
+// ends exactly at hdr, holds a fragment header and does not go on behind hdr. nh: the last extension's next header.
+bool walk_v6_chain(const uint8_t* ip, uint32_t hdr, uint32_t& nh)
+{
+	nh = ip[6];
+	uint32_t at = 40;
+	bool frag = false;
+	while (at + 2 <= hdr && is_v6_extension(nh))
 	{
-		if (!valid_defrag(b, r, max_layers, info, s, o))
-			return PCPPX_E_INVAL;
-		const uint32_t n = b->n;
-		struct Frag
+		const uint32_t len8 = ip[at + 1];
+		frag = frag || nh == 44;
+		const uint32_t ext = nh == 44 ? 8u : nh == 51 ? (len8 + 2) * 4 : (len8 + 1) * 8;
+		nh = ip[at];
+		at += ext;
+	}
+	return at == hdr && frag && !is_v6_extension(nh);
+}
+
+// pcppx_defrag_reference and pcppx_defrag6_reference behind their argument checks: one set of group rules
+int defrag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_reasm_info* info,
+                     const DefragRules* s, pcppx_defragged* o)
+{
+	const uint32_t n = b->n;
+	struct Frag
+	{
+		uint32_t idx, foff, len, ip_off, hdr;
+		bool last, v6;
+	};
+	// every packet's disposition; the candidates by key, in source order
+	std::vector<uint8_t> disp(n, PCPPX_DEFRAG_PASS);
+	std::map<uint32_t, std::vector<Frag>> groups;
+	uint64_t candidates = 0, bad = 0;
+	uint32_t stride = 0;
+	const uint8_t* nlc = n != 0 ? n_layers_column(r, stride) : nullptr;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		uint64_t off;
+		uint32_t cap;
+		if (out_of_bounds(b, 0, i, off, cap))
 		{
-			uint32_t idx, foff, len, ip_off, hdr;
-			bool last;
-		};
-		// every packet's disposition; the candidates by key, in source order
-		std::vector<uint8_t> disp(n, PCPPX_DEFRAG_PASS);
-		std::map<uint32_t, std::vector<Frag>> groups;
-		uint64_t candidates = 0, bad = 0;
-		uint32_t stride = 0;
-		const uint8_t* nlc = n != 0 ? n_layers_column(r, stride) : nullptr;
-		for (uint32_t i = 0; i < n; ++i)
+			disp[i] = PCPPX_DEFRAG_BAD_DESC;
+			++bad;
+			continue;
+		}
+		const uint8_t st = info[i].ip_status;
+		if ((st & 15) != PCPPX_IPR_FRAGMENT)
+			continue;
+		disp[i] = PCPPX_DEFRAG_LEFT;  // until its group turns out clean
+		// families = V4: an IPv6 fragment stays outside the groups. Else both families form them, and the one the spec
+		// does not ask for keeps its groups (and those it shares a key with) from being clean
+		const bool v6 = (st & PCPPX_IPR_F_IPV6) != 0;
+		if (v6 && s->families == PCPPX_DEFRAG_FAM_V4)
+			continue;
+		const uint32_t proto = v6 ? 3 : 2, min_hdr = v6 ? 48 : 20;  // pcpp::IPv6 / pcpp::IPv4: the first such layer
+		const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
+		for (uint32_t k = 0; k < nl; ++k)
 		{
-			uint64_t off;
-			uint32_t cap;
-			if (out_of_bounds(b, 0, i, off, cap))
-			{
-				disp[i] = PCPPX_DEFRAG_BAD_DESC;
-				++bad;
+			const pcppx_layer& L = r->layers[(size_t)i * max_layers + k];
+			if (L.proto != proto)
 				continue;
+			if (L.hdr_len >= min_hdr && L.hdr_len <= L.data_len && (uint32_t)L.offset + L.data_len <= cap)
+			{
+				groups[info[i].ip_key].push_back({ i, info[i].frag_offset, (uint32_t)(L.data_len - L.hdr_len), L.offset,
+				                                   L.hdr_len, (st & PCPPX_IPR_F_LAST) != 0, v6 });
+				++candidates;
 			}
-			const uint8_t st = info[i].ip_status;
-			if ((st & 15) != PCPPX_IPR_FRAGMENT)
-				continue;
-			disp[i] = PCPPX_DEFRAG_LEFT;  // until its group turns out clean
-			if (st & PCPPX_IPR_F_IPV6)
-				continue;
-			const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
-			for (uint32_t k = 0; k < nl; ++k)
+			break;
+		}
+	}
+	for (int k = 0; k < PCPPX_DEFRAG_TOTALS; ++k)
+		o->totals[k] = 0;
+	o->totals[PCPPX_DEFRAG_CANDIDATES] = candidates;
+	o->totals[PCPPX_DEFRAG_BAD_DESC_N] = bad;
+	if (candidates > (s->max_fragments == 0 ? n : s->max_fragments))  // no room to form the groups
+	{
+		o->totals[PCPPX_DEFRAG_OVERFLOW] = 1;
+		return PCPPX_OK;
+	}
+	// the clean groups: members sorted by (frag_offset, source index), keyed by the completing member
+	struct Packet
+	{
+		std::vector<Frag> members;
+		uint32_t total;
+	};
+	std::map<uint32_t, Packet> done;
+	uint64_t merged = 0;
+	// what the packet keeps of the first member's IP header: an IPv6 one loses its extensions
+	auto kept = [](const Frag& f) { return f.v6 ? 40u : f.hdr; };
+	for (auto& kv : groups)
+	{
+		std::vector<Frag>& m = kv.second;
+		if (m.size() < 2 || m.size() > PCPPX_DEFRAG_MAX_FRAGS)
+			continue;
+		std::sort(m.begin(), m.end(),
+		          [](const Frag& x, const Frag& y) { return x.foff != y.foff ? x.foff < y.foff : x.idx < y.idx; });
+		uint32_t total = 0;
+		bool clean = true;
+		for (size_t k = 0; k < m.size() && clean; ++k)
+		{
+			clean = m[k].len > 0 && m[k].foff == total && m[k].last == (k + 1 == m.size()) && m[k].v6 == m[0].v6;
+			total += m[k].len;
+		}
+		if (!clean || m[0].ip_off + m[0].hdr + total > PCPPX_MAX_CAPLEN || m[0].hdr + total > 65535)
+			continue;
+		if ((s->families & (m[0].v6 ? PCPPX_DEFRAG_FAM_V6 : PCPPX_DEFRAG_FAM_V4)) == 0)
+			continue;
+		uint32_t nh;
+		if (m[0].v6 && !walk_v6_chain(b->data + b->offsets[m[0].idx] + m[0].ip_off, m[0].hdr, nh))
+			continue;
+		uint32_t at = 0;
+		for (const Frag& f : m)
+		{
+			disp[f.idx] = PCPPX_DEFRAG_MERGED;
+			at = std::max(at, f.idx);
+		}
+		disp[at] = PCPPX_DEFRAG_MERGED_LAST;
+		merged += m.size();
+		done[at] = Packet{ m, total };
+	}
+	// the output's size, then (all or nothing) the output itself, in source order
+	uint64_t out_packets = 0, out_bytes = 0, left = 0;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		left += disp[i] == PCPPX_DEFRAG_LEFT;
+		if (disp[i] == PCPPX_DEFRAG_MERGED_LAST)
+		{
+			const Packet& p = done[i];
+			++out_packets;
+			out_bytes += p.members[0].ip_off + kept(p.members[0]) + p.total;
+		}
+		else if (s->passthrough && (disp[i] == PCPPX_DEFRAG_PASS || disp[i] == PCPPX_DEFRAG_LEFT))
+		{
+			++out_packets;
+			out_bytes += b->caplens[i];
+		}
+	}
+	const bool overflow = out_packets > o->max_packets || (o->data != nullptr && out_bytes > o->data_cap);
+	o->totals[PCPPX_DEFRAG_OUT_PACKETS] = out_packets;
+	o->totals[PCPPX_DEFRAG_OUT_BYTES] = out_bytes;
+	o->totals[PCPPX_DEFRAG_REASSEMBLED] = done.size();
+	o->totals[PCPPX_DEFRAG_MERGED_FRAGS] = merged;
+	o->totals[PCPPX_DEFRAG_LEFT_FRAGS] = left;
+	o->totals[PCPPX_DEFRAG_OVERFLOW] = overflow ? 1 : 0;
+	if (overflow)
+		return PCPPX_OK;
+	uint32_t j = 0;
+	uint64_t pos = 0;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		if (o->disposition != nullptr)
+			o->disposition[i] = disp[i];
+		uint32_t len, first = i;
+		uint8_t frags = 0;
+		if (disp[i] == PCPPX_DEFRAG_MERGED_LAST)
+		{
+			const Packet& p = done[i];
+			const Frag& f = p.members[0];
+			len = f.ip_off + kept(f) + p.total;
+			first = f.idx;
+			frags = (uint8_t)p.members.size();
+			if (o->data != nullptr)
 			{
-				const pcppx_layer& L = r->layers[(size_t)i * max_layers + k];
-				if (L.proto != 2)  // pcpp::IPv4: the first such layer
-					continue;
-				if (L.hdr_len >= 20 && L.hdr_len <= L.data_len && (uint32_t)L.offset + L.data_len <= cap)
+				uint8_t* d = o->data + pos;
+				std::memcpy(d, b->data + b->offsets[f.idx], f.ip_off + kept(f));
+				for (const Frag& x : p.members)
+					std::memcpy(d + f.ip_off + kept(f) + x.foff, b->data + b->offsets[x.idx] + x.ip_off + x.hdr, x.len);
+				uint8_t* ip = d + f.ip_off;
+				const uint32_t tot_len = f.hdr + p.total;
+				if (f.v6)
 				{
-					groups[info[i].ip_key].push_back({ i, info[i].frag_offset, (uint32_t)(L.data_len - L.hdr_len), L.offset,
-					                                   L.hdr_len, (st & PCPPX_IPR_F_LAST) != 0 });
-					++candidates;
+					// IPReassembly.cpp:476 stores hdr + total without htobe16, the parse of :481 clamps the layer to
+					// that value read as big-endian (IPv6Layer.cpp:37-39), computeCalculateFields writes it back;
+					// removeAllExtensions leaves the last extension's next header
+					const uint32_t swapped = ((tot_len & 0xFFu) << 8) | (tot_len >> 8);
+					const uint32_t plen = std::min(p.total, swapped);
+					uint32_t nh;
+					walk_v6_chain(b->data + b->offsets[f.idx] + f.ip_off, f.hdr, nh);
+					ip[4] = (uint8_t)(plen >> 8);
+					ip[5] = (uint8_t)plen;
+					ip[6] = (uint8_t)nh;
 				}
-				break;
-			}
-		}
-		for (int k = 0; k < PCPPX_DEFRAG_TOTALS; ++k)
-			o->totals[k] = 0;
-		o->totals[PCPPX_DEFRAG_CANDIDATES] = candidates;
-		o->totals[PCPPX_DEFRAG_BAD_DESC_N] = bad;
-		if (candidates > (s->max_fragments == 0 ? n : s->max_fragments))  // no room to form the groups
-		{
-			o->totals[PCPPX_DEFRAG_OVERFLOW] = 1;
-			return PCPPX_OK;
-		}
-		// the clean groups: members sorted by (frag_offset, source index), keyed by the completing member
-		struct Packet
-		{
-			std::vector<Frag> members;
-			uint32_t total;
-		};
-		std::map<uint32_t, Packet> done;
-		uint64_t merged = 0;
-		for (auto& kv : groups)
-		{
-			std::vector<Frag>& m = kv.second;
-			if (m.size() < 2 || m.size() > PCPPX_DEFRAG_MAX_FRAGS)
-				continue;
-			std::sort(m.begin(), m.end(),
-			          [](const Frag& x, const Frag& y) { return x.foff != y.foff ? x.foff < y.foff : x.idx < y.idx; });
-			uint32_t total = 0;
-			bool clean = true;
-			for (size_t k = 0; k < m.size() && clean; ++k)
-			{
-				clean = m[k].len > 0 && m[k].foff == total && m[k].last == (k + 1 == m.size());
-				total += m[k].len;
-			}
-			if (!clean || m[0].ip_off + m[0].hdr + total > PCPPX_MAX_CAPLEN || m[0].hdr + total > 65535)
-				continue;
-			uint32_t at = 0;
-			for (const Frag& f : m)
-			{
-				disp[f.idx] = PCPPX_DEFRAG_MERGED;
-				at = std::max(at, f.idx);
-			}
-			disp[at] = PCPPX_DEFRAG_MERGED_LAST;
-			merged += m.size();
-			done[at] = Packet{ m, total };
-		}
-		// the output's size, then (all or nothing) the output itself, in source order
-		uint64_t out_packets = 0, out_bytes = 0, left = 0;
-		for (uint32_t i = 0; i < n; ++i)
-		{
-			left += disp[i] == PCPPX_DEFRAG_LEFT;
-			if (disp[i] == PCPPX_DEFRAG_MERGED_LAST)
-			{
-				const Packet& p = done[i];
-				++out_packets;
-				out_bytes += p.members[0].ip_off + p.members[0].hdr + p.total;
-			}
-			else if (s->passthrough && (disp[i] == PCPPX_DEFRAG_PASS || disp[i] == PCPPX_DEFRAG_LEFT))
-			{
-				++out_packets;
-				out_bytes += b->caplens[i];
-			}
-		}
-		const bool overflow = out_packets > o->max_packets || (o->data != nullptr && out_bytes > o->data_cap);
-		o->totals[PCPPX_DEFRAG_OUT_PACKETS] = out_packets;
-		o->totals[PCPPX_DEFRAG_OUT_BYTES] = out_bytes;
-		o->totals[PCPPX_DEFRAG_REASSEMBLED] = done.size();
-		o->totals[PCPPX_DEFRAG_MERGED_FRAGS] = merged;
-		o->totals[PCPPX_DEFRAG_LEFT_FRAGS] = left;
-		o->totals[PCPPX_DEFRAG_OVERFLOW] = overflow ? 1 : 0;
-		if (overflow)
-			return PCPPX_OK;
-		uint32_t j = 0;
-		uint64_t pos = 0;
-		for (uint32_t i = 0; i < n; ++i)
-		{
-			if (o->disposition != nullptr)
-				o->disposition[i] = disp[i];
-			uint32_t len, first = i;
-			uint8_t frags = 0;
-			if (disp[i] == PCPPX_DEFRAG_MERGED_LAST)
-			{
-				const Packet& p = done[i];
-				const Frag& f = p.members[0];
-				len = f.ip_off + f.hdr + p.total;
-				first = f.idx;
-				frags = (uint8_t)p.members.size();
-				if (o->data != nullptr)
+				else
 				{
-					uint8_t* d = o->data + pos;
-					std::memcpy(d, b->data + b->offsets[f.idx], f.ip_off + f.hdr + f.len);
-					for (size_t k = 1; k < p.members.size(); ++k)
-					{
-						const Frag& x = p.members[k];
-						std::memcpy(d + f.ip_off + f.hdr + x.foff, b->data + b->offsets[x.idx] + x.ip_off + x.hdr, x.len);
-					}
 					// the header as computeCalculateFields leaves it: total length, no fragment word, the checksum
-					uint8_t* ip = d + f.ip_off;
-					const uint32_t tot_len = f.hdr + p.total;
 					ip[2] = (uint8_t)(tot_len >> 8);
 					ip[3] = (uint8_t)tot_len;
 					ip[6] = ip[7] = ip[10] = ip[11] = 0;
@@ -1688,26 +1757,68 @@ extern "C"
 					ip[11] = (uint8_t)~sum;
 				}
 			}
-			else if (s->passthrough && (disp[i] == PCPPX_DEFRAG_PASS || disp[i] == PCPPX_DEFRAG_LEFT))
-			{
-				len = b->caplens[i];
-				if (o->data != nullptr && len != 0)
-					std::memcpy(o->data + pos, b->data + b->offsets[i], len);
-			}
-			else
-				continue;
-			o->offsets[j] = pos;
-			o->caplens[j] = len;
-			if (o->index != nullptr)
-				o->index[j] = i;
-			if (o->first != nullptr)
-				o->first[j] = first;
-			if (o->frags != nullptr)
-				o->frags[j] = frags;
-			++j;
-			pos += len;
 		}
-		return PCPPX_OK;
+		else if (s->passthrough && (disp[i] == PCPPX_DEFRAG_PASS || disp[i] == PCPPX_DEFRAG_LEFT))
+		{
+			len = b->caplens[i];
+			if (o->data != nullptr && len != 0)
+				std::memcpy(o->data + pos, b->data + b->offsets[i], len);
+		}
+		else
+			continue;
+		o->offsets[j] = pos;
+		o->caplens[j] = len;
+		if (o->index != nullptr)
+			o->index[j] = i;
+		if (o->first != nullptr)
+			o->first[j] = first;
+		if (o->frags != nullptr)
+			o->frags[j] = frags;
+		++j;
+		pos += len;
+	}
+	return PCPPX_OK;
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_defrag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                        const pcppx_reasm_info* info, const pcppx_defrag_spec* s, pcppx_defragged* o,
+	                        void* hip_stream)
+	{
+		DefragRules rules;
+		if (c == nullptr || !valid_defrag(b, r, max_layers, info, s, o, rules))
+			return PCPPX_E_INVAL;
+		return defrag_device(c, b, r, max_layers, info, rules, o, hip_stream);
+	}
+
+	int pcppx_defrag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                           const pcppx_reasm_info* info, const pcppx_defrag_spec* s, pcppx_defragged* o)
+	{
+		DefragRules rules;
+		if (!valid_defrag(b, r, max_layers, info, s, o, rules))
+			return PCPPX_E_INVAL;
+		return defrag_reference(b, r, max_layers, info, &rules, o);
+	}
+
+	int pcppx_defrag6_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                         const pcppx_reasm_info* info, const pcppx_defrag6_spec* s, pcppx_defragged* o,
+	                         void* hip_stream)
+	{
+		DefragRules rules;
+		if (c == nullptr || !valid_defrag6(b, r, max_layers, info, s, o, rules))
+			return PCPPX_E_INVAL;
+		return defrag_device(c, b, r, max_layers, info, rules, o, hip_stream);
+	}
+
+	int pcppx_defrag6_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                            const pcppx_reasm_info* info, const pcppx_defrag6_spec* s, pcppx_defragged* o)
+	{
+		DefragRules rules;
+		if (!valid_defrag6(b, r, max_layers, info, s, o, rules))
+			return PCPPX_E_INVAL;
+		return defrag_reference(b, r, max_layers, info, &rules, o);
 	}
 }
 

@@ -1,6 +1,10 @@
-// pcppx_defrag.hip — pcppx_defrag_device: reassemble the IPv4 fragment groups that are complete inside one batch in HBM.
+// pcppx_defrag.hip — pcppx_defrag_device / pcppx_defrag6_device: reassemble the IPv4 (and IPv6) fragment groups that are
+// complete inside one batch in HBM.
 //
-// The contract is in include/pcppx.h (defrag). Plain launches in stream order; no block waits on another, no thread
+// The contract is in include/pcppx.h (defrag, defrag6). Every kernel but the base one is a template over k6: <false> is
+// pcppx_defrag_device's and pcppx_defrag6_device's with families = V4 (IPv6 fragments never enter the table), <true>
+// takes the fragments of both families as candidates (a family the spec does not ask for only poisons its keys) and
+// adds the IPv6 edges: the layer a candidate is, the first member's extension chain, its two pieces and its patch. Plain launches in stream order; no block waits on another, no thread
 // spins: every table probe is bounded by the table's size, every list walk by PCPPX_DEFRAG_MAX_FRAGS + 1.
 //   (clear)                the group table's keys, counts, list heads, maxima and in-place counts; the candidate counter
 //   defrag_collect_kernel  per kDefragBlockPk-packet block: the candidates (an IPv4 fragment whose IPv4 layer is
@@ -12,9 +16,11 @@
 //                          sets, the counts and maxima are sums and maxima.
 //   defrag_verdict_kernel  per candidate: a walk over its group's list: the members that sort before it by
 //                          (frag_offset, source index) and the sum of their len. It is in place iff that sum is its
-//                          frag_offset, its len > 0 and it has F_LAST exactly when nothing sorts after it; the member
-//                          nothing sorts before also checks the two size bounds and notes itself and the total. A
-//                          group is clean iff all of its 2..64 members are in place (a count). Quadratic in the group.
+//                          frag_offset, its len > 0 and it has F_LAST exactly when nothing sorts after it (<true>: and
+//                          every member is of its family, one the spec asks for); the member nothing sorts before
+//                          also checks the two size bounds (<true>, IPv6: and walks its extension chain) and notes
+//                          itself and the total. A group is clean iff all of its 2..64 members are in place (a count).
+//                          Quadratic in the group.
 //   defrag_count_kernel    per block: output packets and bytes, reassembled / merged / left / bad packets
 //   defrag_base_kernel     one wave: exclusive prefix of the block sums, the totals, the all-or-nothing verdict
 //   defrag_place_kernel    exits on overflow. Per block, each wave its four 64-packet tiles: a wave scan gives the rank
@@ -23,12 +29,18 @@
 //                          as one flattened list over the 64 lanes, then each packet's head and tail); a reassembled
 //                          packet's position goes to its group's slot
 //   defrag_merge_kernel    per candidate of a clean group: its piece to its place in the group's packet (the first
-//                          member: its bytes up to the end of its IP payload), 64 candidates per wave, the same copy
-//   defrag_patch_kernel    per clean group: total length, fragment word and header checksum of the reassembled packet,
-//                          computed from the first member's source bytes (no read of what the merge kernel stored)
+//                          member: its bytes up to the end of its IP payload), 64 candidates per wave, the same copy.
+//                          An IPv6 group: every member's payload behind the fixed header, and in a second round of
+//                          the same copy the first member's bytes up to the end of its fixed header (the extensions
+//                          between the two pieces are cut)
+//   defrag_patch_kernel    per clean group: total length, fragment word and header checksum of the reassembled packet
+//                          (IPv6: payload length and next header), computed from the first member's source bytes (no
+//                          read of what the merge kernel stored)
 // All byte positions are 64-bit. Source bytes are read only through aligned 16-B granules (or single bytes) that hold
 // a byte of a packet that is emitted or merged; destination bytes only inside the packet's own span.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "pcppx.h"
 #include "pcppx_internal.h"
@@ -46,6 +58,8 @@ static_assert(kDfThreads == kDefragCandPerBlock, "one thread per candidate");
 static_assert(PCPPX_DEFRAG_MAX_FRAGS <= 255, "frags[] is a byte");
 constexpr uint32_t kDfUnroll = 4;  // 16-B chunks a lane has in flight in the copy loop
 constexpr uint32_t kProtoIPv4 = 2;  // pcpp::IPv4
+constexpr uint32_t kProtoIPv6 = 3;  // pcpp::IPv6
+constexpr uint32_t kV6Fixed = 40;   // sizeof(ip6_hdr)
 constexpr uint32_t kDfAhead = 4;    // layer entries classify loads ahead of the chain's length
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr unsigned long long kOccupied = 1ull << 32;
@@ -54,7 +68,7 @@ enum : uint32_t
 {
 	kNone,    // past the batch's end
 	kBad,     // descriptor out of bounds
-	kPass,    // not an IPv4 fragment
+	kPass,    // not a fragment
 	kLeft,    // a fragment the device leaves to the host
 	kCand,    // classify only: a candidate, its group not looked at yet
 	kMerged,  // member of a clean group
@@ -98,6 +112,7 @@ struct DfIn
 	uint32_t nl_stride;
 	const pcppx_reasm_info* info;
 	uint32_t passthrough;
+	uint32_t families;  // PCPPX_DEFRAG_FAM_*: the families whose groups may be clean
 };
 
 struct DfOut
@@ -118,7 +133,9 @@ struct DfOut
 // descriptor, when in bounds. Records that point outside the packet make it kLeft: nothing is read there.
 // Dependent loads are what a fragment costs here, so they go out in two rounds: the descriptor with the status, then
 // the chain's length with its first kDfAhead entries (entries past n_layers are unspecified, but inside the row) and
-// the key; only a deeper IPv4 layer takes a load per entry.
+// the key; only a deeper IPv4 layer takes a load per entry. k6: an IPv6 fragment is a candidate by its first IPv6 layer
+// (hdr: the fixed header and the extensions, at least the fragment header; len: what the records say lies behind them).
+template <bool k6>
 __device__ __forceinline__ uint32_t classify(const DfIn& p, uint64_t i, uint64_t& off, uint32_t& cap, Cand& c)
 {
 	off = 0;
@@ -130,8 +147,10 @@ __device__ __forceinline__ uint32_t classify(const DfIn& p, uint64_t i, uint64_t
 		return kBad;
 	if ((st & 15) != PCPPX_IPR_FRAGMENT)
 		return kPass;
-	if (st & PCPPX_IPR_F_IPV6)
+	if (!k6 && (st & PCPPX_IPR_F_IPV6) != 0)
 		return kLeft;
+	const bool v6 = k6 && (st & PCPPX_IPR_F_IPV6) != 0;
+	const uint32_t proto = v6 ? kProtoIPv6 : kProtoIPv4, min_hdr = v6 ? kV6Fixed + 8 : 20u;
 	const pcppx_layer* lay = p.layers + i * p.ml;
 	pcppx_layer ahead[kDfAhead];
 #pragma unroll
@@ -144,7 +163,7 @@ __device__ __forceinline__ uint32_t classify(const DfIn& p, uint64_t i, uint64_t
 	bool found = false;
 #pragma unroll
 	for (uint32_t k = 0; k < kDfAhead; ++k)
-		if (!found && k < nl && ahead[k].proto == kProtoIPv4)
+		if (!found && k < nl && ahead[k].proto == proto)
 		{
 			L = ahead[k];
 			found = true;
@@ -152,9 +171,9 @@ __device__ __forceinline__ uint32_t classify(const DfIn& p, uint64_t i, uint64_t
 	for (uint32_t k = kDfAhead; !found && k < nl; ++k)
 	{
 		L = lay[k];
-		found = L.proto == kProtoIPv4;
+		found = L.proto == proto;
 	}
-	if (!found || L.hdr_len < 20 || L.hdr_len > L.data_len || (uint32_t)L.offset + L.data_len > cap)
+	if (!found || L.hdr_len < min_hdr || L.hdr_len > L.data_len || (uint32_t)L.offset + L.data_len > cap)
 		return kLeft;
 	c.off = off;
 	c.idx = (uint32_t)i;
@@ -194,6 +213,7 @@ __device__ __forceinline__ uint32_t slot_of(const Table& t, uint32_t key)
 	return kNoSlot;
 }
 
+template <bool k6>
 __global__ __launch_bounds__(kDfThreads) void defrag_collect_kernel(DfIn p, Table t)
 {
 	__shared__ uint32_t s_wave[kDfWaves];  // the waves' candidates
@@ -207,7 +227,7 @@ __global__ __launch_bounds__(kDfThreads) void defrag_collect_kernel(DfIn p, Tabl
 	{
 		uint64_t off;
 		uint32_t cap;
-		const bool is = classify(p, tile_first(kDefragBlockPk, w * kDfTilesPerWave + u) + lane, off, cap, c[u]) == kCand;
+		const bool is = classify<k6>(p, tile_first(kDefragBlockPk, w * kDfTilesPerWave + u) + lane, off, cap, c[u]) == kCand;
 		const uint64_t bal = __ballot(is);
 		ahead[u] = mine + __popcll(bal & ((1ull << lane) - 1));
 		mine += __popcll(bal);
@@ -245,7 +265,34 @@ __global__ __launch_bounds__(kDfThreads) void defrag_collect_kernel(DfIn p, Tabl
 	}
 }
 
-__global__ __launch_bounds__(kDfThreads) void defrag_verdict_kernel(Table t)
+// the next-header values parseExtensions (IPv6Layer.cpp:79-147) takes for an extension
+__device__ __forceinline__ bool is_v6_extension(uint32_t nh)
+{
+	return nh == 0 || nh == 43 || nh == 44 || nh == 51 || nh == 60;
+}
+
+// parseExtensions over the extensions ip[40, hdr) of an IPv6 header at ip, hdr >= 48 bytes that all lie inside the
+// packet: true iff the chain ends exactly at hdr, holds a fragment header and does not go on behind hdr (the
+// reassembled packet's parse would walk on there). nh: the next-header byte of the last extension. At most
+// (hdr - 40) / 8 steps (no extension is shorter than 8 bytes); only bytes of [40, hdr) are read, and byte 6.
+__device__ __forceinline__ bool walk_v6_chain(const uint8_t* ip, uint32_t hdr, uint32_t& nh)
+{
+	nh = ip[6];
+	uint32_t at = kV6Fixed;
+	bool frag = false;
+	for (uint32_t step = 0; step < (hdr - kV6Fixed) / 8 && at + 2 <= hdr && is_v6_extension(nh); ++step)
+	{
+		const uint32_t len8 = ip[at + 1];
+		frag = frag || nh == 44;
+		const uint32_t ext = nh == 44 ? 8u : nh == 51 ? (len8 + 2) * 4 : (len8 + 1) * 8;
+		nh = ip[at];
+		at += ext;
+	}
+	return at == hdr && frag && !is_v6_extension(nh);
+}
+
+template <bool k6>
+__global__ __launch_bounds__(kDfThreads) void defrag_verdict_kernel(DfIn p, Table t)
 {
 	const uint32_t nc = t.counters[0];
 	const uint32_t r = blockIdx.x * kDfThreads + threadIdx.x;
@@ -258,12 +305,14 @@ __global__ __launch_bounds__(kDfThreads) void defrag_verdict_kernel(Table t)
 	const uint32_t cnt = t.count[s];
 	if (cnt < 2 || cnt > PCPPX_DEFRAG_MAX_FRAGS)
 		return;
-	uint32_t before = 0, sum_before = 0, after = 0, total = 0, steps = 0;
+	uint32_t before = 0, sum_before = 0, after = 0, total = 0, steps = 0, mixed = 0;
 	uint32_t m = t.head[s];
 	while (m != 0 && steps <= PCPPX_DEFRAG_MAX_FRAGS)  // at most MAX_FRAGS + 1 steps
 	{
 		const Cand c = t.cand[m - 1];
 		total += c.len;
+		if constexpr (k6)
+			mixed |= (c.flags ^ me.flags) & PCPPX_IPR_F_IPV6;
 		if (c.foff < me.foff || (c.foff == me.foff && c.idx < me.idx))
 		{
 			++before;
@@ -277,9 +326,17 @@ __global__ __launch_bounds__(kDfThreads) void defrag_verdict_kernel(Table t)
 	if (m != 0 || steps != cnt)  // the walk hit its bound: not clean
 		return;
 	bool ok = me.len > 0 && sum_before == me.foff && ((me.flags & PCPPX_IPR_F_LAST) != 0) == (after == 0);
+	const bool v6 = k6 && (me.flags & PCPPX_IPR_F_IPV6) != 0;
+	if constexpr (k6)  // one family, and one the spec asks for
+		ok = ok && mixed == 0 && (p.families & (v6 ? PCPPX_DEFRAG_FAM_V6 : PCPPX_DEFRAG_FAM_V4)) != 0;
 	if (before == 0)  // the first member: the bounds of the whole packet
 	{
 		ok = ok && (uint32_t)me.ip_off + me.hdr + total <= PCPPX_MAX_CAPLEN && (uint32_t)me.hdr + total <= 65535u;
+		if (ok && v6)  // its extensions are what the reference will cut
+		{
+			uint32_t nh;
+			ok = walk_v6_chain(p.data + me.off + me.ip_off, me.hdr, nh);
+		}
 		if (ok)
 		{
 			t.grp_first[s] = r;
@@ -292,12 +349,13 @@ __global__ __launch_bounds__(kDfThreads) void defrag_verdict_kernel(Table t)
 
 // packet i's part in the output: its kind (never kCand), whether it puts a packet out and of what length, and for
 // kMerged / kLast its group's slot
+template <bool k6>
 __device__ __forceinline__ uint32_t role(const DfIn& p, const Table& t, uint64_t i, uint64_t& off, bool& emit,
                                          uint32_t& out_len, uint32_t& slot)
 {
 	uint32_t cap;
 	Cand c;
-	uint32_t kind = classify(p, i, off, cap, c);
+	uint32_t kind = classify<k6>(p, i, off, cap, c);
 	slot = kNoSlot;
 	if (kind == kCand)
 	{
@@ -314,13 +372,15 @@ __device__ __forceinline__ uint32_t role(const DfIn& p, const Table& t, uint64_t
 	if (kind == kLast)
 	{
 		const Cand f = t.cand[t.grp_first[slot]];
-		out_len = (uint32_t)f.ip_off + f.hdr + t.grp_total[slot];
+		const bool v6 = k6 && (f.flags & PCPPX_IPR_F_IPV6) != 0;  // its extensions are cut
+		out_len = (uint32_t)f.ip_off + (v6 ? kV6Fixed : (uint32_t)f.hdr) + t.grp_total[slot];
 	}
 	else if (emit)
 		out_len = cap;
 	return kind;
 }
 
+template <bool k6>
 __global__ __launch_bounds__(kDfThreads) void defrag_count_kernel(DfIn p, Table t, uint64_t* __restrict__ bbytes,
                                                                   uint32_t* __restrict__ bcnt,
                                                                   uint32_t* __restrict__ bsums)
@@ -340,12 +400,12 @@ __global__ __launch_bounds__(kDfThreads) void defrag_count_kernel(DfIn p, Table 
 		uint32_t kind, out_len = 0, slot;
 		bool emit = false;
 		if (grouped)
-			kind = role(p, t, i, off, emit, out_len, slot);
+			kind = role<k6>(p, t, i, off, emit, out_len, slot);
 		else
 		{
 			uint32_t cap;
 			Cand cd;
-			kind = classify(p, i, off, cap, cd) == kBad ? kBad : kNone;
+			kind = classify<k6>(p, i, off, cap, cd) == kBad ? kBad : kNone;
 		}
 		b += out_len;
 		c[0] += __popcll(__ballot(emit));
@@ -477,6 +537,7 @@ __device__ __forceinline__ void copy_spans(const uint8_t* sbase, uint8_t* dbase,
 	copy_edge(sbase, dbase, s0 + (ts - q), ts, st ? (uint32_t)(e - ts) : 0u);
 }
 
+template <bool k6>
 __global__ __launch_bounds__(kDfThreads) void defrag_place_kernel(DfIn p, Table t, DfOut o,
                                                                   const uint64_t* __restrict__ base_bytes,
                                                                   const uint32_t* __restrict__ base_cnt)
@@ -501,7 +562,7 @@ __global__ __launch_bounds__(kDfThreads) void defrag_place_kernel(DfIn p, Table 
 		uint64_t off;
 		uint32_t out_len, slot;
 		bool emit;
-		const uint32_t kind = role(p, t, tile_first(kDefragBlockPk, tl) + lane, off, emit, out_len, slot);
+		const uint32_t kind = role<k6>(p, t, tile_first(kDefragBlockPk, tl) + lane, off, emit, out_len, slot);
 		s_off[tl][lane] = off;
 		s_len[tl][lane] = out_len;
 		s_slot[tl][lane] = slot;
@@ -577,6 +638,7 @@ __device__ __forceinline__ uint32_t clean_slot(const Table& t, const DfOut& o, u
 	return (s != kNoSlot && t.inplace[s] == t.count[s]) ? s : kNoSlot;
 }
 
+template <bool k6>
 __global__ __launch_bounds__(kDfThreads) void defrag_merge_kernel(DfIn p, Table t, DfOut o)
 {
 	__shared__ uint64_t s_cp[kDfWaves][65];
@@ -589,13 +651,25 @@ __global__ __launch_bounds__(kDfThreads) void defrag_merge_kernel(DfIn p, Table 
 	const bool st = s != kNoSlot;
 	if (__ballot(st) == 0)
 		return;
-	uint64_t src = 0, dst = 0;
-	uint32_t len = 0;
+	uint64_t src = 0, dst = 0, src2 = 0, dst2 = 0;
+	uint32_t len = 0, len2 = 0;  // 2: the first IPv6 member's second piece
 	if (st)
 	{
 		const uint32_t fr = t.grp_first[s];
 		const Cand f = t.cand[fr];
-		if (fr == r)  // the first member: its bytes up to the end of its IP payload (a trailer is dropped)
+		if (k6 && (c.flags & PCPPX_IPR_F_IPV6) != 0)  // every member's payload behind the first one's fixed header
+		{
+			src = c.off + c.ip_off + c.hdr;
+			dst = t.grp_pos[s] + f.ip_off + kV6Fixed + c.foff;
+			len = c.len;
+			if (fr == r)  // and the first member's bytes up to the end of its fixed header: its extensions are cut
+			{
+				src2 = c.off;
+				dst2 = t.grp_pos[s];
+				len2 = (uint32_t)c.ip_off + kV6Fixed;
+			}
+		}
+		else if (fr == r)  // the first member: its bytes up to the end of its IP payload (a trailer is dropped)
 		{
 			src = c.off;
 			dst = t.grp_pos[s];
@@ -611,8 +685,15 @@ __global__ __launch_bounds__(kDfThreads) void defrag_merge_kernel(DfIn p, Table 
 	const auto [dbase, dal] = align16(o.data);
 	const auto [sbase, sal] = align16(p.data);
 	copy_spans(sbase, dbase, lane, st, src + sal, dst + dal, len, s_cp[w], s_dq[w], s_sa[w]);
+	if constexpr (k6)
+	{
+		const bool st2 = len2 != 0;
+		if (__ballot(st2) != 0)
+			copy_spans(sbase, dbase, lane, st2, src2 + sal, dst2 + dal, len2, s_cp[w], s_dq[w], s_sa[w]);
+	}
 }
 
+template <bool k6>
 __global__ __launch_bounds__(kDfThreads) void defrag_patch_kernel(DfIn p, Table t, DfOut o)
 {
 	const uint32_t r = blockIdx.x * kDfThreads + threadIdx.x;
@@ -622,6 +703,20 @@ __global__ __launch_bounds__(kDfThreads) void defrag_patch_kernel(DfIn p, Table 
 		return;
 	const uint32_t tot_len = (uint32_t)c.hdr + t.grp_total[s];  // <= 65535
 	const uint8_t* ip = p.data + c.off + c.ip_off;
+	if (k6 && (c.flags & PCPPX_IPR_F_IPV6) != 0)
+	{
+		// IPReassembly.cpp:476 stores hdr + total without htobe16; the parse of :481 clamps the layer to that value read
+		// as big-endian (IPv6Layer.cpp:37-39), and computeCalculateFields writes the clamped length back
+		const uint32_t swapped = ((tot_len & 0xFFu) << 8) | (tot_len >> 8), total = t.grp_total[s];
+		const uint32_t plen = total < swapped ? total : swapped;
+		uint32_t nh;
+		walk_v6_chain(ip, c.hdr, nh);  // removeAllExtensions: the last extension's next header
+		uint8_t* d = o.data + t.grp_pos[s] + c.ip_off;
+		d[4] = (uint8_t)(plen >> 8);
+		d[5] = (uint8_t)plen;
+		d[6] = (uint8_t)nh;
+		return;
+	}
 	// the RFC 1071 sum over the header as it will stand: words 1 (total length), 3 (flags / fragment offset) and 5
 	// (checksum) replaced; an odd last byte (no real header has one) is padded with zero
 	uint32_t sum = tot_len;
@@ -669,10 +764,10 @@ uint64_t defrag_scratch_bytes(uint32_t n, uint32_t max_fragments)
 }
 
 int launch_defrag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
-                  uint32_t nl_stride, const pcppx_reasm_info* info, const pcppx_defrag_spec* spec,
-                  const pcppx_defragged* out, void* scratch, hipStream_t stream)
+                  uint32_t nl_stride, const pcppx_reasm_info* info, uint32_t max_fragments, uint32_t passthrough,
+                  uint32_t families, const pcppx_defragged* out, void* scratch, hipStream_t stream)
 {
-	const uint32_t g = defrag_blocks(b->n), F = defrag_room(b->n, spec->max_fragments), C = defrag_slots(F);
+	const uint32_t g = defrag_blocks(b->n), F = defrag_room(b->n, max_fragments), C = defrag_slots(F);
 	uint32_t lg = 0;
 	while ((1u << lg) < C)
 		++lg;
@@ -702,21 +797,30 @@ int launch_defrag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, 
 	if (hipMemsetAsync(scratch, 0, 16 + 24ull * C, stream) != hipSuccess)
 		return PCPPX_E_HIP;
 	DfIn in{ b->data, b->offsets, b->caplens, b->data_len, b->n,        layers,
-		     ml,      n_layers,   nl_stride,  info,        spec->passthrough };
+		     ml,      n_layers,   nl_stride,  info,        passthrough, families };
 	DfOut o{ out->data,  out->data_cap, out->offsets,     out->caplens,     out->index,
 		     out->first, out->frags,    out->disposition, out->max_packets, out->totals };
 	const uint32_t gc = (F + kDefragCandPerBlock - 1) / kDefragCandPerBlock;
-	hipLaunchKernelGGL(defrag_collect_kernel, dim3(g), dim3(kDfThreads), 0, stream, in, t);
-	hipLaunchKernelGGL(defrag_verdict_kernel, dim3(gc), dim3(kDfThreads), 0, stream, t);
-	hipLaunchKernelGGL(defrag_count_kernel, dim3(g), dim3(kDfThreads), 0, stream, in, t, bbytes, bcnt, bsums);
-	hipLaunchKernelGGL(defrag_base_kernel, dim3(1), dim3(64), 0, stream, g, t, bbytes, bcnt, bsums, base_bytes, base_cnt,
-	                   o, spec->max_fragments == 0 ? b->n : spec->max_fragments);
-	hipLaunchKernelGGL(defrag_place_kernel, dim3(g), dim3(kDfThreads), 0, stream, in, t, o, base_bytes, base_cnt);
-	if (out->data != nullptr)
-	{
-		hipLaunchKernelGGL(defrag_merge_kernel, dim3(gc), dim3(kDfThreads), 0, stream, in, t, o);
-		hipLaunchKernelGGL(defrag_patch_kernel, dim3(gc), dim3(kDfThreads), 0, stream, in, t, o);
-	}
+	const uint32_t cap = max_fragments == 0 ? b->n : max_fragments;
+	// families = V4: pcppx_defrag_device's kernels; else the ones that know both families
+	auto launch = [&](auto k6) {
+		constexpr bool v6 = decltype(k6)::value;
+		hipLaunchKernelGGL(defrag_collect_kernel<v6>, dim3(g), dim3(kDfThreads), 0, stream, in, t);
+		hipLaunchKernelGGL(defrag_verdict_kernel<v6>, dim3(gc), dim3(kDfThreads), 0, stream, in, t);
+		hipLaunchKernelGGL(defrag_count_kernel<v6>, dim3(g), dim3(kDfThreads), 0, stream, in, t, bbytes, bcnt, bsums);
+		hipLaunchKernelGGL(defrag_base_kernel, dim3(1), dim3(64), 0, stream, g, t, bbytes, bcnt, bsums, base_bytes,
+		                   base_cnt, o, cap);
+		hipLaunchKernelGGL(defrag_place_kernel<v6>, dim3(g), dim3(kDfThreads), 0, stream, in, t, o, base_bytes, base_cnt);
+		if (out->data != nullptr)
+		{
+			hipLaunchKernelGGL(defrag_merge_kernel<v6>, dim3(gc), dim3(kDfThreads), 0, stream, in, t, o);
+			hipLaunchKernelGGL(defrag_patch_kernel<v6>, dim3(gc), dim3(kDfThreads), 0, stream, in, t, o);
+		}
+	};
+	if (families == PCPPX_DEFRAG_FAM_V4)
+		launch(std::false_type{});
+	else
+		launch(std::true_type{});
 	return check_launch("defrag", stream);
 }
 }  // namespace pcppx

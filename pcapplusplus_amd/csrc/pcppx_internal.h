@@ -55,8 +55,9 @@ uint32_t steer_blocks(uint32_t n);
 uint64_t steer_scratch_bytes(uint32_t n, uint32_t n_buckets);
 int launch_steer(const pcppx_batch* b, const pcppx_steer_spec* spec, const pcppx_steering* out, void* scratch,
                  hipStream_t stream);
-// pcppx_defrag_device (pcppx_defrag.hip): one clear and five to seven launches on `stream` (collect, verdict, count,
-// bases, place; with out->data the merge copy and the header patch). scratch: defrag_scratch_bytes(n, max_fragments)
+// pcppx_defrag_device / pcppx_defrag6_device (pcppx_defrag.hip): one clear and five to seven launches on `stream`
+// (collect, verdict, count, bases, place; with out->data the merge copy and the header patch); families: the
+// PCPPX_DEFRAG_FAM_* bits (V4 alone: pcppx_defrag_device's kernels). scratch: defrag_scratch_bytes(n, max_fragments)
 // bytes (include/pcppx.h gives the formula); one block takes kDefragBlockPk packets, the verdict / merge / patch
 // kernels kDefragCandPerBlock candidates; n_layers: packet 0's n_layers byte (a summary's or a brief's), nl_stride
 // bytes apart. Arguments are checked by the caller; n > 0.
@@ -68,8 +69,8 @@ uint32_t defrag_room(uint32_t n, uint32_t max_fragments);  // F: the candidates 
 uint32_t defrag_slots(uint32_t room);                      // C: the group table's slots
 uint64_t defrag_scratch_bytes(uint32_t n, uint32_t max_fragments);
 int launch_defrag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
-                  uint32_t nl_stride, const pcppx_reasm_info* info, const pcppx_defrag_spec* spec,
-                  const pcppx_defragged* out, void* scratch, hipStream_t stream);
+                  uint32_t nl_stride, const pcppx_reasm_info* info, uint32_t max_fragments, uint32_t passthrough,
+                  uint32_t families, const pcppx_defragged* out, void* scratch, hipStream_t stream);
 // pcppx_tcpstream_device (pcppx_tcpstream.hip): two clears and nine launches on `stream` (collect, second sides, join,
 // chain, verdict, count, bases, place, emit). scratch: tcpstream_scratch_bytes(n, max_segments) bytes (include/pcppx.h
 // gives the formula); one block takes kTcpsBlockPk packets, the per-candidate kernels kTcpsCandPerBlock candidates;

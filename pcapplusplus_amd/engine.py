@@ -197,6 +197,23 @@ class Engine:
         (i64) / out_caplens (i32) / out_index / out_first (i32) / out_frags (u8) of max_packets entries, disposition
         (u8[n]), each of the last four optional; totals: 8 x i64 (abi.DEFRAG_*), overwritten. All or nothing: on
         overflow only the totals are written. Returns without waiting."""
+        self._defrag("pcppx_defrag_device", data, offsets, caplens, n, linktype, layers, max_layers, info, spec,
+                     out_offsets, out_caplens, totals, max_packets, out_data, data_cap, out_index, out_first, out_frags,
+                     disposition, stream, data_len, summary, brief)
+
+    def defrag6_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, info,
+                       spec: abi.Defrag6Spec, out_offsets, out_caplens, totals, max_packets: int, out_data=None,
+                       data_cap: int = 0, out_index=None, out_first=None, out_frags=None, disposition=None,
+                       stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_defrag6_device over device tensors: defrag_device for the families spec.families names (the
+        IPv6 fragment groups are reassembled too). The arguments are defrag_device's."""
+        self._defrag("pcppx_defrag6_device", data, offsets, caplens, n, linktype, layers, max_layers, info, spec,
+                     out_offsets, out_caplens, totals, max_packets, out_data, data_cap, out_index, out_first, out_frags,
+                     disposition, stream, data_len, summary, brief)
+
+    def _defrag(self, call: str, data, offsets, caplens, n, linktype, layers, max_layers, info, spec, out_offsets,
+                out_caplens, totals, max_packets, out_data, data_cap, out_index, out_first, out_frags, disposition,
+                stream, data_len, summary, brief) -> None:
         b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
                       int(data.numel()) if data_len is None else data_len, n, linktype, 0)
         opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
@@ -204,9 +221,8 @@ class Engine:
         rec.brief = opt(brief)
         out = abi.Defragged(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
                             opt(out_first), opt(out_frags), opt(disposition), max_packets, 0, abi.ptr(totals))
-        abi.check(self.lib.pcppx_defrag_device(self.ctx, C.byref(b), C.byref(rec), max_layers, abi.ptr(info),
-                                               C.byref(spec), C.byref(out), C.c_void_p(stream or 0)),
-                  "pcppx_defrag_device")
+        abi.check(getattr(self.lib, call)(self.ctx, C.byref(b), C.byref(rec), max_layers, abi.ptr(info),
+                                          C.byref(spec), C.byref(out), C.c_void_p(stream or 0)), call)
 
     def tcpstream_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, info,
                          spec: abi.TcpStreamSpec, streams, totals, max_streams: int, out_data=None, data_cap: int = 0,
@@ -704,9 +720,19 @@ def tcpstream_on_device(eng: Engine, batch: PacketBatch, records, layers, info, 
             seg_pos[:k].cpu().numpy().view(np.uint32), tot)
 
 
+def defrag6_on_device(eng: Engine, batch: PacketBatch, records, layers, info, passthrough: bool = True,
+                      max_fragments: int = 0, families: int = abi.DEFRAG_FAM_V4 | abi.DEFRAG_FAM_V6,
+                      data_cap: int | None = None, max_packets: int | None = None, index_only: bool = False,
+                      device: str = "cuda:0"):
+    """defrag_on_device through pcppx_defrag6_device: the fragment groups of the families named (abi.DEFRAG_FAM_* bits)
+    are reassembled, the IPv6 ones too. Arguments and results are defrag_on_device's."""
+    return defrag_on_device(eng, batch, records, layers, info, passthrough, max_fragments, data_cap, max_packets,
+                            index_only, device, families)
+
+
 def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, passthrough: bool = True,
                      max_fragments: int = 0, data_cap: int | None = None, max_packets: int | None = None,
-                     index_only: bool = False, device: str = "cuda:0"):
+                     index_only: bool = False, device: str = "cuda:0", families: int | None = None):
     """Copy a host batch and its parse to HBM, reassemble there the IPv4 fragment groups that are complete inside the
     batch (pcppx_defrag_device), copy the result back: (PacketBatch of the output packets in source order; index u32 =
     their source packet numbers, a reassembled packet's being the completing fragment's; first u32 = the packet whose
@@ -717,7 +743,8 @@ def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, pas
     is not merged (IPDefragUtil's output), else only the reassembled packets come out. data_cap / max_packets default
     to the batch's bytes / packets and max_fragments to n (always enough). All or nothing: when totals["overflow"] is
     set the returned batch and columns are empty. timestamps_ns follow the packets through first, frame_lens through
-    index (a reassembled packet's frame length is its own length)."""
+    index (a reassembled packet's frame length is its own length). families: None, or the abi.DEFRAG_FAM_* bits for
+    pcppx_defrag6_device (defrag6_on_device)."""
     import torch
 
     n = batch.n
@@ -741,10 +768,13 @@ def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, pas
     disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
     totals = torch.empty(abi.DEFRAG_TOTALS, dtype=torch.int64, device=device)
     is_brief = rec.dtype.itemsize == abi.BRIEF_DTYPE.itemsize
-    eng.defrag_device(data, offsets, caplens, n, batch.linktype, lay_t, ml, info_t,
-                      abi.make_defrag_spec(passthrough, max_fragments), out_off, out_cap, totals, mp, out_data, cap,
-                      out_idx, out_first, out_frags, disp, torch.cuda.current_stream(device).cuda_stream,
-                      summary=None if is_brief else rec_t, brief=rec_t if is_brief else None)
+    if families is None:
+        call, spec = eng.defrag_device, abi.make_defrag_spec(passthrough, max_fragments)
+    else:
+        call, spec = eng.defrag6_device, abi.make_defrag6_spec(passthrough, max_fragments, families)
+    call(data, offsets, caplens, n, batch.linktype, lay_t, ml, info_t, spec, out_off, out_cap, totals, mp, out_data, cap,
+         out_idx, out_first, out_frags, disp, torch.cuda.current_stream(device).cuda_stream,
+         summary=None if is_brief else rec_t, brief=rec_t if is_brief else None)
     torch.cuda.synchronize(device)
     tot = abi.defrag_totals_dict(totals.cpu().numpy().view(np.uint64))
     w, wb = (0, 0) if tot["overflow"] else (tot["out_packets"], tot["out_bytes"])
