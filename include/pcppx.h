@@ -994,6 +994,100 @@ PCPPX_API int pcppx_frag_device(pcppx_ctx* ctx, const pcppx_batch* batch, const 
 PCPPX_API int pcppx_frag_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                    const pcppx_frag_spec* spec, pcppx_fragmented* out);
 
+/* ---- frag6: frag for both families: the IPv6 packets of a device batch are split into fragments too ----
+ * splitIPPacketToFragmentsBySize handles both families in one routine (Examples/IPFragUtil/main.cpp:153-238);
+ * pcppx_frag_device labels every IPv6 packet NOT_V4 because the reference draws the IPv6 fragment id with rand(). Here
+ * the ids are an input column, so the output stays a pure function of the inputs and that departure is closed: this
+ * call takes the families the spec names. Everything not said here is pcppx_frag_device's contract: the inputs,
+ * pcppx_fragmented, the totals words, the output order, keep and copy_rest, the all-or-nothing capacity rule, the
+ * index-only sizing call, the 16-B granule rule, determinism (no atomics), n == 0, the scratch formula (52 g + 12 n
+ * bytes: the plan's words are shared by the two families) and the stream ordering (the two calls share one scratch
+ * buffer and event per context). Added within ABI 7: new symbols only. With families = PCPPX_FRAG_FAM_V4 every
+ * output column and every byte equals pcppx_frag_device's (the same kernels run) and ids / id_base are ignored.
+ *
+ * Which layer (main.cpp:159-172: IPv4 if the packet has any IPv4 layer, else the first IPv6 layer). With V4 | V6: the
+ * first recorded IPv4 layer if there is one, by frag's rule and with frag's dispositions (a 6in4 packet is split at
+ * its IPv4 header, a 4in6 packet at its inner IPv4 header); otherwise the first layer of protocol IPv6 among the first
+ * min(n_layers, max_layers) entries. With V6: a packet that records an IPv4 layer is NOT_IP (its datagram is the IPv4
+ * one, and that family was not asked for); otherwise its first IPv6 layer is taken.
+ *
+ * The IPv6 candidate: ip_off = layer.offset, hdr = layer.hdr_len (the fixed header and every extension
+ * parseExtensions walked, Packet++/src/IPv6Layer.cpp:79-147) and pay = layer.data_len - hdr (getLayerPayloadSize():
+ * the records' value, with the constructor's clamp to payloadLength + getHeaderLen() already in it,
+ * IPv6Layer.cpp:37-39). Required: 40 <= hdr <= data_len and offset + data_len <= caplen; otherwise the packet is
+ * NOT_IP and nothing is read. Then the extension chain is walked from the next-header byte at ip_off + 6 over
+ * [ip_off + 40, ip_off + hdr): types 0, 43 and 60 are (len8 + 1) * 8 bytes long, type 44 is 8, type 51 is
+ * (len8 + 2) * 4. It yields nh_at, the packet offset of the last extension's next-header byte (ip_off + 6 without
+ * extensions), and whether a type-44 header is among them. A chain that does not end exactly at hdr (a next header
+ * that is no extension type ahead of hdr, an extension that crosses hdr) is one the records do not describe: NOT_IP.
+ * The walk takes at most PCPPX_FRAG6_MAX_EXT steps and reads nothing outside [ip_off, ip_off + hdr).
+ *
+ * Disposition of an IPv6 candidate, after BAD_DESC, UNSELECTED and NOT_IP, the first rule that applies:
+ *   1 LEFT     the chain is sound so far but has more than PCPPX_FRAG6_MAX_EXT extensions, or the chain is sound and
+ *              a layer ahead of the IPv6 layer is not Ethernet, VLAN or SLL: the host's
+ *   2 ALREADY  the chain holds a fragment header (the reference would add a second one and restart the offsets at 0:
+ *              the same deliberate departure as for IPv4)
+ *   3 FITS     size mode: pay <= fs; mtu mode: hdr + pay <= mtu
+ *   4 LEFT     mtu mode only: mtu < hdr + 16 (no room for 8 payload bytes behind the fragment header)
+ *   5 SPLIT    with fs = frag_size, or in mtu mode (mtu - hdr - 8) & ~7
+ * honor_df has no meaning for IPv6 and is ignored there. LEFT packets are copied under copy_rest, as every other
+ * unsplit packet.
+ *
+ * Fragments of a SPLIT IPv6 packet (main.cpp:124-128, 185-237; IPv6Layer.h:212-241; IPv6Extensions.cpp:52-69;
+ * IPv6Layer.cpp:314-356): c = ceil(pay / fs) of them, 2 <= c <= 8187. Fragment j is bytes [0, ip_off + hdr) of the
+ * source, then an 8-byte fragment header -- byte 0 the value the byte at nh_at held, byte 1 zero, bytes 2-3
+ * be16((j * fs) | (j < c - 1 ? 1 : 0)), bytes 4-7 be32(id) -- then its payload bytes [j * fs, min((j + 1) * fs, pay)),
+ * `piece` bytes. In the copied part the byte at nh_at becomes 44 and bytes ip_off + 4..5 become
+ * be16(hdr - 40 + 8 + piece). Nothing else changes from ip_off on: there is no checksum, a trailer is dropped. Its caplen is
+ * ip_off + hdr + 8 + piece, which can exceed the source's caplen by up to 7 bytes (the movers emit any caplen). The
+ * fragment id of source packet i is ids ? ids[i] : (uint32_t)(id_base + i), wrapping at 2^32.
+ *
+ * The layers ahead of the IPv6 header. Packet::computeCalculateFields runs over every layer of a fragment, and the
+ * layers in front recompute fields of their own: a PPPoE or GRE v1 length, a tunnel's UDP length and checksum, and so
+ * on, per fragment. So an IPv6 candidate is split only if every layer recorded ahead of its IPv6 layer is Ethernet,
+ * VLAN or SLL (none at all: raw IP); any other layer there makes it LEFT (rule 1 below), decided from the records
+ * alone. Of those three, each sets its type field from the layer behind it (EthLayer.cpp:71-93, VlanLayer.cpp:121-143,
+ * SllLayer.cpp:104-126), which changes a byte in one case only: ahead of a VLAN layer the field becomes 0x8100, so an
+ * 802.1ad tag's 0x88A8 is renamed. Every fragment carries that: for each layer k ahead of the IPv6 layer whose
+ * successor k + 1 is a VLAN layer with 2 <= offset <= ip_off, bytes offset - 2 and offset - 1 are 0x81 0x00 (written,
+ * never read). tests/golden/frag6 records it behind Ethernet, VLAN and SLL. (pcppx_frag_device copies those bytes.)
+ *
+ * Sizes: a SPLIT IPv6 packet puts out c * (ip_off + hdr + 8) + pay bytes, so frag's closed bound gains 8 * c_i:
+ *   OUT_BYTES <= sum caplen_i + sum (c_i - 1) * head_i + 8 * sum c_i,
+ * and from the descriptors alone, with F = frag_size in size mode and in mtu mode
+ * F = min((mtu - 60) & ~7, (mtu - H - 8) & ~7), H = min(the largest IPv6 hdr in the batch, mtu - 16) (a packet with
+ * hdr > mtu - 16 is never split; H = mtu - 16 always holds and gives F = 8),
+ *   OUT_PACKETS <= sum max(1, ceil(caplen_i / F))   and
+ *   OUT_BYTES <= sum (caplen_i + caplen_i^2 / (4 F) + 8 * ceil(caplen_i / F)).
+ * Source bytes are read as in frag, and as single bytes of the IPv6 header and extensions of an in-bounds, selected
+ * packet. An IPv6 fragment's bytes differ from the source's only in the places named above.
+ *
+ * PCPPX_E_INVAL before any device work: frag's list, and families 0 or with a bit above PCPPX_FRAG_FAM_V6. */
+#define PCPPX_FRAG_FAM_V4 1
+#define PCPPX_FRAG_FAM_V6 2
+#define PCPPX_FRAG6_MAX_EXT 16
+/* two more pcppx_fragmented.disposition values */
+#define PCPPX_FRAG_NOT_IP PCPPX_FRAG_NOT_V4 /* no layer of a family the spec asks for, as defined above */
+#define PCPPX_FRAG_LEFT 7                   /* an IPv6 packet this call does not split and the reference would */
+typedef struct pcppx_frag6_spec {
+	const uint8_t* keep; /* as pcppx_frag_spec */
+	uint32_t frag_size;
+	uint32_t mtu;
+	uint8_t copy_rest;
+	uint8_t honor_df;    /* IPv4 packets only */
+	uint8_t families;    /* PCPPX_FRAG_FAM_* bits; 0 or bits above 3: PCPPX_E_INVAL */
+	uint8_t reserved[5]; /* 0 */
+	const uint32_t* ids; /* device, n entries: the fragment id of source packet i. NULL: (uint32_t)(id_base + i) */
+	uint32_t id_base;
+	uint32_t reserved2;  /* 0 */
+} pcppx_frag6_spec;
+PCPPX_API int pcppx_frag6_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                 uint8_t max_layers, const pcppx_frag6_spec* spec, pcppx_fragmented* out,
+                                 void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_frag6_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                    const pcppx_frag6_spec* spec, pcppx_fragmented* out);
+
 /* ---- tlsfp: JA3 / JA3S TLS fingerprints of the hello packets of a device batch (TLSFingerprinting) ----
  * What Examples/TLSFingerprinting does with SSLClientHelloMessage::generateTLSFingerprint() and
  * SSLServerHelloMessage::generateTLSFingerprint() and their toStringAndMD5() (Packet++/src/SSLHandshake.cpp:1577-1689,

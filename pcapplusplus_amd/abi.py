@@ -360,6 +360,36 @@ def frag_reference(batch: Batch, records: Records, max_layers: int, spec: FragSp
                                              C.byref(out)), "pcppx_frag_reference")
 
 
+# pcppx_frag6_*: frag for both families (include/pcppx.h, frag6)
+FRAG_FAM_V4, FRAG_FAM_V6 = 1, 2
+FRAG6_MAX_EXT = 16
+FRAG_NOT_IP, FRAG_LEFT = FRAG_NOT_V4, 7  # two more disposition values
+
+
+class Frag6Spec(C.Structure):
+    """pcppx_frag6_spec: pcppx_frag_spec, the families (FRAG_FAM_* bits) whose packets are split, and the IPv6 fragment
+    ids: a device column of n u32, or id_base + i."""
+    _fields_ = [("keep", C.c_void_p), ("frag_size", C.c_uint32), ("mtu", C.c_uint32), ("copy_rest", C.c_uint8),
+                ("honor_df", C.c_uint8), ("families", C.c_uint8), ("reserved", C.c_uint8 * 5), ("ids", C.c_void_p),
+                ("id_base", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+def make_frag6_spec(frag_size: int = 0, mtu: int = 0, families: int = FRAG_FAM_V4 | FRAG_FAM_V6, ids=None,
+                    id_base: int = 0, keep=None, copy_rest: bool = True, honor_df: bool = False) -> Frag6Spec:
+    """make_frag_spec's arguments; families: the FRAG_FAM_* bits; ids: the address of the n-entry u32 column of
+    fragment ids (None: source packet i gets (id_base + i) mod 2^32)."""
+    s = Frag6Spec(keep, frag_size, mtu, 1 if copy_rest else 0, 1 if honor_df else 0, families)
+    s.ids, s.id_base = ids, id_base & 0xFFFFFFFF
+    return s
+
+
+def frag6_reference(batch: Batch, records: Records, max_layers: int, spec: Frag6Spec, out: Fragmented) -> None:
+    """pcppx_frag6_reference: pcppx_frag6_device's contract in plain C++ over host pointers (no GPU); the arguments
+    are frag_reference's."""
+    check(load_engine().pcppx_frag6_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                              C.byref(out)), "pcppx_frag6_reference")
+
+
 # pcppx_tlsfp_*: JA3 / JA3S fingerprints of the hello packets of a batch (include/pcppx.h, tlsfp)
 TLSFP_NONE, TLSFP_CLIENT, TLSFP_SERVER, TLSFP_HOST, TLSFP_BAD_DESC = range(5)  # disposition; CLIENT / SERVER: rec.kind
 (TLSFP_CLIENT_N, TLSFP_SERVER_N, TLSFP_TEXT_BYTES, TLSFP_HOST_N, TLSFP_BAD_DESC_N, TLSFP_CANDIDATES, _TLSFP_ZERO,
@@ -784,6 +814,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_frag_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(FragSpec),
                                          C.POINTER(Fragmented)]
     lib.pcppx_frag_reference.restype = C.c_int
+    lib.pcppx_frag6_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(Frag6Spec),
+                                       C.POINTER(Fragmented), P]
+    lib.pcppx_frag6_device.restype = C.c_int
+    lib.pcppx_frag6_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(Frag6Spec),
+                                          C.POINTER(Fragmented)]
+    lib.pcppx_frag6_reference.restype = C.c_int
     lib.pcppx_tlsfp_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(TlsfpSpec),
                                        C.POINTER(Tlsfps), P]
     lib.pcppx_tlsfp_device.restype = C.c_int
@@ -829,7 +865,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_unpack_layers", "pcppx_unpack_layers_brief", "pcppx_window_choice",
     "pcppx_select_device", "pcppx_select_reference", "pcppx_steer_device", "pcppx_steer_reference",
     "pcppx_defrag_device", "pcppx_defrag_reference", "pcppx_defrag6_device", "pcppx_defrag6_reference",
-    "pcppx_frag_device", "pcppx_frag_reference",
+    "pcppx_frag_device", "pcppx_frag_reference", "pcppx_frag6_device", "pcppx_frag6_reference",
     "pcppx_tcpstream_device", "pcppx_tcpstream_reference", "pcppx_tlsfp_device", "pcppx_tlsfp_reference",
     "pcppx_dns_device", "pcppx_dns_reference",
     "pcppx_http_device", "pcppx_http_reference",

@@ -1933,12 +1933,12 @@ extern "C"
 	}
 }
 
-// ---- frag: the IPv4 packets of a batch split into fragments (include/pcppx.h, frag) ----
+// ---- frag: the IPv4 / IPv6 packets of a batch split into fragments (include/pcppx.h, frag, frag6) ----
 namespace
 {
-// the argument rules pcppx_frag_device and pcppx_frag_reference share (include/pcppx.h)
-bool valid_frag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag_spec* s,
-                const pcppx_fragmented* o)
+// the argument rules the four frag calls share; a pcppx_frag_spec arrives as a pcppx_frag6_spec with families = V4
+bool valid_frag6(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag6_spec* s,
+                 const pcppx_fragmented* o)
 {
 	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->offsets == nullptr ||
 	    o->caplens == nullptr)
@@ -1951,7 +1951,9 @@ bool valid_frag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers
 		return false;
 	if (s->mtu != 0 && (s->mtu < 68 || s->mtu > 65535))
 		return false;
-	if (s->copy_rest > 1 || s->honor_df > 1 || o->reserved != 0)
+	if (s->copy_rest > 1 || s->honor_df > 1 || o->reserved != 0 || s->reserved2 != 0)
+		return false;
+	if (s->families == 0 || (s->families & ~(PCPPX_FRAG_FAM_V4 | PCPPX_FRAG_FAM_V6)) != 0)
 		return false;
 	for (uint8_t x : s->reserved)
 		if (x != 0)
@@ -1960,137 +1962,238 @@ bool valid_frag(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers
 		return false;
 	return valid_batch(b);
 }
-}  // namespace
 
-extern "C"
+// pcppx_frag_spec as the spec both families share: families = V4, no ids. False where its own reserved bytes are set.
+bool widen_frag_spec(const pcppx_frag_spec* s, pcppx_frag6_spec& w)
 {
-	int pcppx_frag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
-	                      const pcppx_frag_spec* s, pcppx_fragmented* o, void* hip_stream)
-	{
-		if (c == nullptr || !valid_frag(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_FRAG_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous frag (possibly queued on another stream) owns the plans until it is done
-		int rc = c->frag.acquire(st, pcppx::frag_scratch_bytes(b->n));
-		if (rc != PCPPX_OK)
-			return rc;
-		uint32_t stride;
-		const uint8_t* nl = n_layers_column(r, stride);
-		rc = pcppx::launch_frag(b, r->layers, max_layers, nl, stride, s, o, c->frag.ptr, st);
-		return rc != PCPPX_OK ? rc : c->frag.mark_used(st);
-	}
+	w = pcppx_frag6_spec{};
+	if (s == nullptr)
+		return false;
+	for (uint8_t x : s->reserved)
+		if (x != 0)
+			return false;
+	w.keep = s->keep;
+	w.frag_size = s->frag_size;
+	w.mtu = s->mtu;
+	w.copy_rest = s->copy_rest;
+	w.honor_df = s->honor_df;
+	w.families = PCPPX_FRAG_FAM_V4;
+	return true;
+}
 
-	int pcppx_frag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag_spec* s,
-	                         pcppx_fragmented* o)
+// pcppx_frag_device and pcppx_frag6_device behind their argument checks
+int frag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+                const pcppx_frag6_spec* s, pcppx_fragmented* o, void* hip_stream)
+{
+	if (!ok(hipSetDevice(c->device)))
+		return PCPPX_E_HIP;
+	hipStream_t st = static_cast<hipStream_t>(hip_stream);
+	if (b->n == 0)
+		return ok(hipMemsetAsync(o->totals, 0, PCPPX_FRAG_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+	// the context's previous frag (possibly queued on another stream) owns the plans until it is done
+	int rc = c->frag.acquire(st, pcppx::frag_scratch_bytes(b->n));
+	if (rc != PCPPX_OK)
+		return rc;
+	uint32_t stride;
+	const uint8_t* nl = n_layers_column(r, stride);
+	rc = pcppx::launch_frag(b, r->layers, max_layers, nl, stride, s, o, c->frag.ptr, st);
+	return rc != PCPPX_OK ? rc : c->frag.mark_used(st);
+}
+
+// a source packet as both references see it
+struct FragSrc
+{
+	uint8_t disp;
+	bool v6;
+	uint32_t ip_off, hdr, pay, fs, count;  // of a SPLIT packet
+	uint32_t nh_at;                        // IPv6: the packet offset of the last next-header byte
+};
+
+// The disposition of in-bounds packet i (packet bytes pk, caplen cap) and, for a SPLIT packet, its shape: the one
+// per-packet routine of pcppx_frag_reference and pcppx_frag6_reference.
+uint8_t frag_classify(const pcppx_records* r, uint8_t max_layers, const uint8_t* nlc, uint32_t stride,
+                      const pcppx_frag6_spec* s, uint32_t i, const uint8_t* pk, uint32_t cap, FragSrc& x)
+{
+	if (s->keep != nullptr && s->keep[i] == 0)
+		return PCPPX_FRAG_UNSELECTED;
+	const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
+	const pcppx_layer* L = nullptr;
+	const pcppx_layer* L6 = nullptr;
+	bool plain = true;  // every layer ahead of the IPv6 one is Ethernet, VLAN or SLL
+	for (uint32_t k = 0; k < nl; ++k)
 	{
-		if (!valid_frag(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		const uint32_t n = b->n;
-		struct Src
+		const pcppx_layer* X = &r->layers[(size_t)i * max_layers + k];
+		if (X->proto == 2 && L == nullptr)  // pcpp::IPv4: the first such layer
+			L = X;
+		if (X->proto == 3 && L6 == nullptr)  // pcpp::IPv6
+			L6 = X;
+		if (L6 == nullptr)
+			plain = plain && (X->proto == 1 || X->proto == 9 || X->proto == 19);
+	}
+	if (L != nullptr || (s->families & PCPPX_FRAG_FAM_V6) == 0)
+	{
+		if (L == nullptr || (s->families & PCPPX_FRAG_FAM_V4) == 0 || L->hdr_len < 20 || L->hdr_len > 60 ||
+		    L->hdr_len > L->data_len || (uint32_t)L->offset + L->data_len > cap)
+			return PCPPX_FRAG_NOT_V4;
+		x.ip_off = L->offset;
+		x.hdr = L->hdr_len;
+		x.pay = (uint32_t)L->data_len - L->hdr_len;
+		x.fs = s->frag_size != 0 ? s->frag_size : ((s->mtu - x.hdr) & ~7u);
+		const uint8_t* ip = pk + x.ip_off;
+		const uint32_t word = ((uint32_t)ip[6] << 8) | ip[7];
+		if ((word & 0x3FFFu) != 0)
+			return PCPPX_FRAG_ALREADY;
+		if (s->frag_size != 0 ? x.pay <= x.fs : x.hdr + x.pay <= s->mtu)
+			return PCPPX_FRAG_FITS;
+		if (s->honor_df != 0 && (word & 0x4000u) != 0)
+			return PCPPX_FRAG_DF;
+		return PCPPX_FRAG_SPLIT;
+	}
+	if (L6 == nullptr || L6->hdr_len < 40 || L6->hdr_len > L6->data_len || (uint32_t)L6->offset + L6->data_len > cap)
+		return PCPPX_FRAG_NOT_IP;
+	x.v6 = true;
+	x.ip_off = L6->offset;
+	x.hdr = L6->hdr_len;
+	x.pay = (uint32_t)L6->data_len - L6->hdr_len;
+	// parseExtensions over [40, hdr): it must end exactly at hdr
+	const uint8_t* ip = pk + x.ip_off;
+	uint32_t nh = ip[6], at = 40, steps = 0;
+	bool fragmented = false;
+	x.nh_at = x.ip_off + 6;
+	while (at < x.hdr)
+	{
+		if (!is_v6_extension(nh) || at + 2 > x.hdr)
+			return PCPPX_FRAG_NOT_IP;
+		if (steps++ == PCPPX_FRAG6_MAX_EXT)
+			return PCPPX_FRAG_LEFT;
+		const uint32_t len8 = ip[at + 1];
+		fragmented = fragmented || nh == 44;
+		x.nh_at = x.ip_off + at;
+		const uint32_t ext = nh == 44 ? 8u : nh == 51 ? (len8 + 2) * 4 : (len8 + 1) * 8;
+		nh = ip[at];
+		at += ext;
+	}
+	if (at != x.hdr)
+		return PCPPX_FRAG_NOT_IP;
+	if (!plain)
+		return PCPPX_FRAG_LEFT;
+	if (fragmented)
+		return PCPPX_FRAG_ALREADY;
+	if (s->frag_size != 0 ? x.pay <= s->frag_size : x.hdr + x.pay <= s->mtu)
+		return PCPPX_FRAG_FITS;
+	if (s->frag_size == 0 && s->mtu < x.hdr + 16)
+		return PCPPX_FRAG_LEFT;
+	x.fs = s->frag_size != 0 ? s->frag_size : ((s->mtu - x.hdr - 8) & ~7u);
+	return PCPPX_FRAG_SPLIT;
+}
+
+// pcppx_frag_reference and pcppx_frag6_reference behind their argument checks
+int frag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag6_spec* s,
+                   pcppx_fragmented* o)
+{
+	const uint32_t n = b->n;
+	std::vector<FragSrc> src(n);
+	uint32_t stride = 0;
+	const uint8_t* nlc = n != 0 ? n_layers_column(r, stride) : nullptr;
+	uint64_t out_packets = 0, out_bytes = 0, split = 0, fragments = 0, copied = 0, fits = 0, bad = 0;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		FragSrc& x = src[i];
+		x = FragSrc{ PCPPX_FRAG_BAD_DESC, false, 0, 0, 0, 0, 0, 0 };
+		uint64_t off;
+		uint32_t cap;
+		if (out_of_bounds(b, 0, i, off, cap))
 		{
-			uint8_t disp;
-			uint32_t ip_off, hdr, pay, fs, count;  // of a SPLIT packet
-		};
-		std::vector<Src> src(n);
-		uint32_t stride = 0;
-		const uint8_t* nlc = n != 0 ? n_layers_column(r, stride) : nullptr;
-		uint64_t out_packets = 0, out_bytes = 0, split = 0, fragments = 0, copied = 0, fits = 0, bad = 0;
-		for (uint32_t i = 0; i < n; ++i)
-		{
-			Src& x = src[i];
-			x = Src{ PCPPX_FRAG_BAD_DESC, 0, 0, 0, 0, 0 };
-			uint64_t off;
-			uint32_t cap;
-			if (out_of_bounds(b, 0, i, off, cap))
-			{
-				++bad;
-				continue;
-			}
-			x.disp = [&]() -> uint8_t {
-				if (s->keep != nullptr && s->keep[i] == 0)
-					return PCPPX_FRAG_UNSELECTED;
-				const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
-				const pcppx_layer* L = nullptr;
-				for (uint32_t k = 0; k < nl && L == nullptr; ++k)
-					if (r->layers[(size_t)i * max_layers + k].proto == 2)  // pcpp::IPv4: the first such layer
-						L = &r->layers[(size_t)i * max_layers + k];
-				if (L == nullptr || L->hdr_len < 20 || L->hdr_len > 60 || L->hdr_len > L->data_len ||
-				    (uint32_t)L->offset + L->data_len > cap)
-					return PCPPX_FRAG_NOT_V4;
-				x.ip_off = L->offset;
-				x.hdr = L->hdr_len;
-				x.pay = (uint32_t)L->data_len - L->hdr_len;
-				x.fs = s->frag_size != 0 ? s->frag_size : ((s->mtu - x.hdr) & ~7u);
-				const uint8_t* ip = b->data + off + x.ip_off;
-				const uint32_t word = ((uint32_t)ip[6] << 8) | ip[7];
-				if ((word & 0x3FFFu) != 0)
-					return PCPPX_FRAG_ALREADY;
-				if (s->frag_size != 0 ? x.pay <= x.fs : x.hdr + x.pay <= s->mtu)
-					return PCPPX_FRAG_FITS;
-				if (s->honor_df != 0 && (word & 0x4000u) != 0)
-					return PCPPX_FRAG_DF;
-				return PCPPX_FRAG_SPLIT;
-			}();
-			fits += x.disp == PCPPX_FRAG_FITS;
-			if (x.disp == PCPPX_FRAG_SPLIT)
-			{
-				x.count = (x.pay + x.fs - 1) / x.fs;
-				++split;
-				fragments += x.count;
-				out_bytes += (uint64_t)x.count * (x.ip_off + x.hdr) + x.pay;
-			}
-			else if (s->copy_rest != 0)
-			{
-				x.count = 1;
-				++copied;
-				out_bytes += cap;
-			}
-			out_packets += x.count;
+			++bad;
+			continue;
 		}
-		const bool overflow = out_packets > o->max_packets || (o->data != nullptr && out_bytes > o->data_cap);
-		o->totals[PCPPX_FRAG_OUT_PACKETS] = out_packets;
-		o->totals[PCPPX_FRAG_OUT_BYTES] = out_bytes;
-		o->totals[PCPPX_FRAG_SPLIT_PACKETS] = split;
-		o->totals[PCPPX_FRAG_FRAGMENTS] = fragments;
-		o->totals[PCPPX_FRAG_COPIED] = copied;
-		o->totals[PCPPX_FRAG_UNDER_SIZE] = fits;
-		o->totals[PCPPX_FRAG_BAD_DESC_N] = bad;
-		o->totals[PCPPX_FRAG_OVERFLOW] = overflow ? 1 : 0;
-		if (overflow)
-			return PCPPX_OK;
-		uint32_t j = 0;
-		uint64_t pos = 0;
-		for (uint32_t i = 0; i < n; ++i)
+		x.disp = frag_classify(r, max_layers, nlc, stride, s, i, b->data + off, cap, x);
+		fits += x.disp == PCPPX_FRAG_FITS;
+		if (x.disp == PCPPX_FRAG_SPLIT)
 		{
-			const Src& x = src[i];
-			if (o->disposition != nullptr)
-				o->disposition[i] = x.disp;
-			if (o->counts != nullptr)
-				o->counts[i] = (uint16_t)x.count;
-			for (uint32_t f = 0; f < x.count; ++f)
+			x.count = (x.pay + x.fs - 1) / x.fs;
+			++split;
+			fragments += x.count;
+			out_bytes += (uint64_t)x.count * (x.ip_off + x.hdr + (x.v6 ? 8u : 0u)) + x.pay;
+		}
+		else if (s->copy_rest != 0)
+		{
+			x.count = 1;
+			++copied;
+			out_bytes += cap;
+		}
+		out_packets += x.count;
+	}
+	const bool overflow = out_packets > o->max_packets || (o->data != nullptr && out_bytes > o->data_cap);
+	o->totals[PCPPX_FRAG_OUT_PACKETS] = out_packets;
+	o->totals[PCPPX_FRAG_OUT_BYTES] = out_bytes;
+	o->totals[PCPPX_FRAG_SPLIT_PACKETS] = split;
+	o->totals[PCPPX_FRAG_FRAGMENTS] = fragments;
+	o->totals[PCPPX_FRAG_COPIED] = copied;
+	o->totals[PCPPX_FRAG_UNDER_SIZE] = fits;
+	o->totals[PCPPX_FRAG_BAD_DESC_N] = bad;
+	o->totals[PCPPX_FRAG_OVERFLOW] = overflow ? 1 : 0;
+	if (overflow)
+		return PCPPX_OK;
+	uint32_t j = 0;
+	uint64_t pos = 0;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		const FragSrc& x = src[i];
+		if (o->disposition != nullptr)
+			o->disposition[i] = x.disp;
+		if (o->counts != nullptr)
+			o->counts[i] = (uint16_t)x.count;
+		for (uint32_t f = 0; f < x.count; ++f)
+		{
+			const uint8_t* from = b->data + b->offsets[i];
+			uint32_t len = b->caplens[i];
+			if (x.disp != PCPPX_FRAG_SPLIT)
 			{
-				const uint8_t* from = b->data + b->offsets[i];
-				uint32_t len = b->caplens[i];
-				if (x.disp != PCPPX_FRAG_SPLIT)
+				if (o->data != nullptr && len != 0)
+					std::memcpy(o->data + pos, from, len);
+			}
+			else
+			{
+				const uint32_t head = x.ip_off + x.hdr, gap = x.v6 ? 8u : 0u, piece = std::min(x.fs, x.pay - f * x.fs);
+				len = head + gap + piece;
+				if (o->data != nullptr)
 				{
-					if (o->data != nullptr && len != 0)
-						std::memcpy(o->data + pos, from, len);
-				}
-				else
-				{
-					const uint32_t head = x.ip_off + x.hdr, piece = std::min(x.fs, x.pay - f * x.fs);
-					len = head + piece;
-					if (o->data != nullptr)
+					uint8_t* d = o->data + pos;
+					std::memcpy(d, from, head);
+					std::memcpy(d + head + gap, from + head + (size_t)f * x.fs, piece);
+					uint8_t* ip = d + x.ip_off;
+					if (x.v6)
 					{
-						uint8_t* d = o->data + pos;
-						std::memcpy(d, from, head);
-						std::memcpy(d + head, from + head + (size_t)f * x.fs, piece);
+						// the fragment header addExtension puts behind the last extension, and the payload length as
+						// computeCalculateFields leaves it
+						const uint32_t id = s->ids != nullptr ? s->ids[i] : s->id_base + i;
+						const uint32_t word = (f * x.fs) | (f + 1 < x.count ? 1u : 0u), plen = x.hdr - 40 + 8 + piece;
+						uint8_t* fh = d + head;
+						fh[0] = d[x.nh_at];
+						fh[1] = 0;
+						fh[2] = (uint8_t)(word >> 8);
+						fh[3] = (uint8_t)word;
+						fh[4] = (uint8_t)(id >> 24);
+						fh[5] = (uint8_t)(id >> 16);
+						fh[6] = (uint8_t)(id >> 8);
+						fh[7] = (uint8_t)id;
+						d[x.nh_at] = 44;
+						ip[4] = (uint8_t)(plen >> 8);
+						ip[5] = (uint8_t)plen;
+						// the type field ahead of a VLAN layer, as the layer in front of it recomputes it
+						const uint32_t nl = std::min<uint32_t>(nlc[(size_t)i * stride], max_layers);
+						const pcppx_layer* lay = &r->layers[(size_t)i * max_layers];
+						for (uint32_t k = 0; k + 1 < nl && lay[k].proto != 3; ++k)
+							if (lay[k + 1].proto == 9 && lay[k + 1].offset >= 2 && lay[k + 1].offset <= x.ip_off)
+							{
+								d[lay[k + 1].offset - 2] = 0x81;
+								d[lay[k + 1].offset - 1] = 0x00;
+							}
+					}
+					else
+					{
 						// the header as setIPv4FragmentParams and computeCalculateFields leave it
-						uint8_t* ip = d + x.ip_off;
 						const uint32_t tot_len = x.hdr + piece, word = (f * x.fs / 8) | (f + 1 < x.count ? 0x2000u : 0u);
 						ip[2] = (uint8_t)(tot_len >> 8);
 						ip[3] = (uint8_t)tot_len;
@@ -2106,17 +2209,55 @@ extern "C"
 						ip[11] = (uint8_t)~sum;
 					}
 				}
-				o->offsets[j] = pos;
-				o->caplens[j] = len;
-				if (o->index != nullptr)
-					o->index[j] = i;
-				if (o->frag_no != nullptr)
-					o->frag_no[j] = (uint16_t)f;
-				++j;
-				pos += len;
 			}
+			o->offsets[j] = pos;
+			o->caplens[j] = len;
+			if (o->index != nullptr)
+				o->index[j] = i;
+			if (o->frag_no != nullptr)
+				o->frag_no[j] = (uint16_t)f;
+			++j;
+			pos += len;
 		}
-		return PCPPX_OK;
+	}
+	return PCPPX_OK;
+}
+}  // namespace
+
+extern "C"
+{
+	int pcppx_frag_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                      const pcppx_frag_spec* s, pcppx_fragmented* o, void* hip_stream)
+	{
+		pcppx_frag6_spec w;
+		if (c == nullptr || !widen_frag_spec(s, w) || !valid_frag6(b, r, max_layers, &w, o))
+			return PCPPX_E_INVAL;
+		return frag_device(c, b, r, max_layers, &w, o, hip_stream);
+	}
+
+	int pcppx_frag_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_frag_spec* s,
+	                         pcppx_fragmented* o)
+	{
+		pcppx_frag6_spec w;
+		if (!widen_frag_spec(s, w) || !valid_frag6(b, r, max_layers, &w, o))
+			return PCPPX_E_INVAL;
+		return frag_reference(b, r, max_layers, &w, o);
+	}
+
+	int pcppx_frag6_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                       const pcppx_frag6_spec* s, pcppx_fragmented* o, void* hip_stream)
+	{
+		if (c == nullptr || !valid_frag6(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		return frag_device(c, b, r, max_layers, s, o, hip_stream);
+	}
+
+	int pcppx_frag6_reference(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                          const pcppx_frag6_spec* s, pcppx_fragmented* o)
+	{
+		if (!valid_frag6(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		return frag_reference(b, r, max_layers, s, o);
 	}
 }
 

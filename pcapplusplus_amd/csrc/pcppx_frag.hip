@@ -1,6 +1,16 @@
-// pcppx_frag.hip — pcppx_frag_device: split the IPv4 packets of a batch in HBM into fragments (IPFragUtil).
+// pcppx_frag.hip — pcppx_frag_device / pcppx_frag6_device: split the IPv4 (and IPv6) packets of a batch in HBM into
+// fragments (IPFragUtil).
 //
-// The contract is in include/pcppx.h (frag). Plain launches in stream order; no block waits on another, no thread
+// The contract is in include/pcppx.h (frag, frag6). Every kernel but the base one is a template over k6: <false> is
+// pcppx_frag_device's and pcppx_frag6_device's with families = V4 (no IPv6 layer is looked for), <true> takes the
+// IPv6 packets too: the plan kernel refines classify()'s verdict (classify_families; classify() itself stays as it
+// was, so that <false> compiles to the instructions it always did), takes the first IPv6 layer of a packet without an
+// IPv4 one, walks its extension chain (at most PCPPX_FRAG6_MAX_EXT steps) and keeps hdr and the place of the last
+// next-header byte in the plan's
+// spare words; an IPv6 fragment is head span, an 8-byte gap, piece span, and the patch kernel alone writes the gap (the
+// fragment header), the next-header byte and the payload length. No span's store touches a gap byte: copy_spans writes
+// exactly [q, q + len) of each span (whole chunks only inside it, its head and tail byte-exact), and the two spans of a
+// fragment end and begin at the gap's two ends. Plain launches in stream order; no block waits on another, no thread
 // spins, no atomics. One source packet puts out up to 8,190 packets, and how many is known only on the device, so
 // every grid is sized from n: a block owns kFragBlockPk source packets and all of their output packets.
 //   frag_plan_kernel   per block, each wave its four 64-packet tiles, a lane per source packet: the disposition from the
@@ -23,6 +33,8 @@
 // that is emitted, or as single bytes of the IPv4 header of an in-bounds, selected packet.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "pcppx.h"
 #include "pcppx_internal.h"
 #include "pcppx_move.h"
@@ -37,16 +49,22 @@ constexpr uint32_t kFrTilesPerWave = 4, kFrTiles = kFrWaves * kFrTilesPerWave;
 static_assert(kFrTiles * 64 == kFragBlockPk, "a block takes kFragBlockPk packets");
 constexpr uint32_t kFrUnroll = 4;   // 16-B chunks a lane has in flight in the copy loop
 constexpr uint32_t kProtoIPv4 = 2;  // pcpp::IPv4
+constexpr uint32_t kProtoIPv6 = 3;  // pcpp::IPv6
+constexpr uint32_t kProtoEth = 1, kProtoVlan = 9, kProtoSll = 19;  // pcpp::Ethernet, VLAN, SLL
+constexpr uint32_t kV6Fixed = 40, kV6FragHdr = 8;
+constexpr uint32_t kPlanV6 = 1u << 31;  // Plan::sum of an IPv6 packet
 constexpr uint32_t kNone = 0xFF;    // a plan's disp past the batch's end (never stored)
 constexpr uint32_t kFrSums = 5;     // split packets, fragments, copied, under size, bad descriptors
 
 // What the later kernels need of a source packet, 12 bytes. ip_off / pay / hdr / sum: of a SPLIT packet only.
 struct Plan
 {
-	uint32_t sum;  // the header's 16-bit words but total length, fragment word and checksum, added up (< 2^21)
+	// IPv4: the header's 16-bit words but total length, fragment word and checksum, added up (< 2^21).
+	// IPv6 (<true> only): kPlanV6 | the offset of the last next-header byte from ip_off (< 2^16)
+	uint32_t sum;
 	uint16_t ip_off, pay;
-	uint8_t hdr, disp;  // PCPPX_FRAG_* or kNone
-	uint16_t pad;
+	uint8_t hdr, disp;  // hdr: IPv4's; disp: PCPPX_FRAG_* or kNone
+	uint16_t hdr6;      // IPv6's hdr: the fixed header and the extensions (0 for IPv4)
 };
 static_assert(sizeof(Plan) == 12, "frag_scratch_bytes");
 
@@ -66,6 +84,15 @@ struct FrIn
 	uint32_t copy_rest, honor_df;
 };
 
+// the <true> kernels' input: the families asked for (V6 is among them) and the fragment ids
+struct FrIn6 : FrIn
+{
+	uint32_t families, id_base;
+	const uint32_t* ids;
+};
+template <bool k6>
+using In = std::conditional_t<k6, FrIn6, FrIn>;
+
 struct FrOut
 {
 	uint8_t* data;  // null: index-only
@@ -84,6 +111,82 @@ struct FrOut
 __device__ __forceinline__ uint32_t frag_fs(const FrIn& p, uint32_t hdr)
 {
 	return p.frag_size != 0 ? p.frag_size : ((p.mtu - hdr) & ~7u);
+}
+
+// A SPLIT packet's plan read for either family: the bytes ahead of the payload (head), the gap behind them that the
+// patch kernel fills (IPv6's fragment header) and the fragment size (IPv6, mtu mode: mtu >= hdr + 16, so fs >= 8)
+template <bool k6>
+__device__ __forceinline__ void split_shape(const FrIn& p, const Plan& pl, uint32_t& head, uint32_t& gap, uint32_t& fs)
+{
+	if constexpr (k6)
+	{
+		if ((pl.sum & kPlanV6) != 0)
+		{
+			head = (uint32_t)pl.ip_off + pl.hdr6;
+			gap = kV6FragHdr;
+			fs = p.frag_size != 0 ? p.frag_size : ((p.mtu - pl.hdr6 - kV6FragHdr) & ~7u);
+			return;
+		}
+	}
+	head = (uint32_t)pl.ip_off + pl.hdr;
+	gap = 0;
+	fs = frag_fs(p, pl.hdr);
+}
+
+__device__ __forceinline__ bool is_v6_extension(uint32_t nh)
+{
+	return nh == 0 || nh == 43 || nh == 44 || nh == 51 || nh == 60;
+}
+
+// The plan of an IPv6 candidate: layer L of the in-bounds, selected packet at batch offset off, caplen cap. Single
+// bytes are read only in [ip_off, ip_off + hdr), which the checks ahead of the walk put inside the packet. plain: every
+// layer recorded ahead of it is Ethernet, VLAN or SLL (else computeCalculateFields changes more than is written here).
+__device__ __forceinline__ Plan classify6(const FrIn6& p, const pcppx_layer& L, uint64_t off, uint32_t cap, bool plain)
+{
+	Plan pl{};
+	pl.disp = PCPPX_FRAG_NOT_IP;
+	if (L.hdr_len < kV6Fixed || L.hdr_len > L.data_len || (uint32_t)L.offset + L.data_len > cap)
+		return pl;
+	const uint32_t hdr = L.hdr_len, pay = (uint32_t)L.data_len - L.hdr_len;
+	const uint8_t* ip = p.data + off + L.offset;
+	uint32_t nh = ip[6], at = kV6Fixed, nh_rel = 6;
+	bool fragmented = false;
+#pragma unroll 1
+	for (uint32_t step = 0; at < hdr; ++step)  // at most PCPPX_FRAG6_MAX_EXT + 1 trips
+	{
+		if (!is_v6_extension(nh) || at + 2 > hdr)
+			return pl;
+		if (step == PCPPX_FRAG6_MAX_EXT)
+		{
+			pl.disp = PCPPX_FRAG_LEFT;
+			return pl;
+		}
+		const uint32_t len8 = ip[at + 1];
+		fragmented = fragmented || nh == 44;
+		nh_rel = at;
+		at += nh == 44 ? 8u : nh == 51 ? (len8 + 2) * 4 : (len8 + 1) * 8;
+		nh = ip[nh_rel];
+	}
+	if (at != hdr)
+		return pl;
+	pl.disp = PCPPX_FRAG_LEFT;
+	if (!plain)
+		return pl;
+	pl.disp = PCPPX_FRAG_ALREADY;
+	if (fragmented)
+		return pl;
+	pl.disp = PCPPX_FRAG_FITS;
+	if (p.frag_size != 0 ? pay <= p.frag_size : hdr + pay <= p.mtu)
+		return pl;
+	pl.disp = PCPPX_FRAG_LEFT;
+	if (p.frag_size == 0 && p.mtu < hdr + 2 * kV6FragHdr)
+		return pl;
+	pl.disp = PCPPX_FRAG_SPLIT;
+	pl.ip_off = L.offset;
+	pl.pay = (uint16_t)pay;
+	pl.hdr6 = (uint16_t)hdr;
+	pl.sum = kPlanV6 | nh_rel;
+	return pl;
 }
 
 // Packet i's plan (disp kNone past the batch's end). cap: its caplen, when the descriptor is in bounds. Records that
@@ -144,16 +247,59 @@ __device__ __forceinline__ Plan classify(const FrIn& p, uint64_t i, uint32_t& ca
 	return pl;
 }
 
+// <true>: packet i's plan for the families asked for, from classify()'s (which knows IPv4 only; cap is its caplen).
+// A packet with an IPv4 layer keeps frag's verdict, or is NOT_IP where IPv4 is not asked for; one without is taken at
+// its first IPv6 layer. Kept apart from classify() so that the code of the <false> kernels stays what it was.
+__device__ __forceinline__ Plan classify_families(const FrIn6& p, uint64_t i, uint32_t cap, const Plan& v4)
+{
+	if (v4.disp == kNone || v4.disp == PCPPX_FRAG_BAD_DESC || v4.disp == PCPPX_FRAG_UNSELECTED)
+		return v4;
+	Plan none{};
+	none.disp = PCPPX_FRAG_NOT_IP;
+	if (v4.disp != PCPPX_FRAG_NOT_V4)  // a sound IPv4 layer decided
+		return (p.families & PCPPX_FRAG_FAM_V4) != 0 ? v4 : none;
+	const pcppx_layer* lay = p.layers + i * p.ml;
+	uint32_t nl = p.n_layers[i * p.nl_stride];
+	nl = nl < p.ml ? nl : p.ml;
+	pcppx_layer L6{};
+	bool found6 = false, plain = true;
+	for (uint32_t k = 0; k < nl; ++k)
+	{
+		const pcppx_layer L = lay[k];
+		if (L.proto == kProtoIPv4)  // recorded, but no header inside the packet: frag's NOT_V4
+			return none;
+		if (!found6 && L.proto == kProtoIPv6)
+		{
+			L6 = L;
+			found6 = true;
+		}
+		if (!found6)
+			plain = plain && (L.proto == kProtoEth || L.proto == kProtoVlan || L.proto == kProtoSll);
+	}
+	return found6 ? classify6(p, L6, p.offsets[i], cap, plain) : none;
+}
+
 // the output packets and bytes of a source packet: a SPLIT packet's fragments, or the packet itself where it is copied
+template <bool k6>
 __device__ __forceinline__ void outputs(const FrIn& p, const Plan& pl, uint32_t cap, uint32_t& cnt, uint64_t& bytes)
 {
 	cnt = 0;
 	bytes = 0;
 	if (pl.disp == PCPPX_FRAG_SPLIT)
 	{
-		const uint32_t fs = frag_fs(p, pl.hdr);
-		cnt = (pl.pay + fs - 1) / fs;  // 2..8190
-		bytes = (uint64_t)cnt * ((uint32_t)pl.ip_off + pl.hdr) + pl.pay;
+		if constexpr (k6)
+		{
+			uint32_t head, gap, fs;
+			split_shape<true>(p, pl, head, gap, fs);
+			cnt = (pl.pay + fs - 1) / fs;  // 2..8190
+			bytes = (uint64_t)cnt * (head + gap) + pl.pay;
+		}
+		else
+		{
+			const uint32_t fs = frag_fs(p, pl.hdr);
+			cnt = (pl.pay + fs - 1) / fs;  // 2..8190
+			bytes = (uint64_t)cnt * ((uint32_t)pl.ip_off + pl.hdr) + pl.pay;
+		}
 	}
 	else if (pl.disp != kNone && pl.disp != PCPPX_FRAG_BAD_DESC && p.copy_rest != 0)
 	{
@@ -162,7 +308,8 @@ __device__ __forceinline__ void outputs(const FrIn& p, const Plan& pl, uint32_t 
 	}
 }
 
-__global__ __launch_bounds__(kFrThreads) void frag_plan_kernel(FrIn p, Plan* __restrict__ plan,
+template <bool k6>
+__global__ __launch_bounds__(kFrThreads) void frag_plan_kernel(In<k6> p, Plan* __restrict__ plan,
                                                                uint64_t* __restrict__ bcnt,
                                                                uint64_t* __restrict__ bbytes,
                                                                uint32_t* __restrict__ bsums)
@@ -179,10 +326,12 @@ __global__ __launch_bounds__(kFrThreads) void frag_plan_kernel(FrIn p, Plan* __r
 		const uint64_t i = tile_first(kFragBlockPk, w * kFrTilesPerWave + u) + lane;
 		uint32_t cap, cnt;
 		uint64_t bytes;
-		const Plan pl = classify(p, i, cap);
+		Plan pl = classify(p, i, cap);
+		if constexpr (k6)
+			pl = classify_families(p, i, cap, pl);
 		if (pl.disp != kNone)
 			plan[i] = pl;
-		outputs(p, pl, cap, cnt, bytes);
+		outputs<k6>(p, pl, cap, cnt, bytes);
 		const bool split = pl.disp == PCPPX_FRAG_SPLIT;
 		c += cnt;
 		b += bytes;
@@ -257,6 +406,7 @@ __global__ __launch_bounds__(64) void frag_base_kernel(uint32_t g, const uint64_
 // kNone past the batch's end) and the exclusive prefixes of their output packets (s_cp) and bytes (s_bp),
 // kFragBlockPk + 1 entries each: the last one is the block's total. s_tc / s_tb: kFrTiles words of scratch. Ends in a
 // block barrier.
+template <bool k6>
 __device__ __forceinline__ void block_prefix(const FrIn& p, const Plan* __restrict__ plan, Plan* s_plan, uint32_t* s_cp,
                                              uint64_t* s_bp, uint32_t* s_tc, uint64_t* s_tb)
 {
@@ -275,7 +425,7 @@ __device__ __forceinline__ void block_prefix(const FrIn& p, const Plan* __restri
 			pl = plan[i];
 			cap = p.caplens[i];
 		}
-		outputs(p, pl, cap, cnt, bytes);
+		outputs<k6>(p, pl, cap, cnt, bytes);
 		s_plan[slot] = pl;
 		const uint64_t ic = wave_scan_incl((uint64_t)cnt, lane), ib = wave_scan_incl(bytes, lane);
 		s_cp[slot] = (uint32_t)(ic - cnt);  // a tile puts out at most 64 * 8190 packets, a block 1024 * 8190
@@ -385,12 +535,14 @@ __device__ __forceinline__ void copy_spans(const uint8_t* sbase, uint8_t* dbase,
 // Output packet r of the block (r below its total): its source packet k of the block, its number j among that packet's
 // output packets, its byte position in the block's output, and for a fragment (fs != 0) its two spans: `head` bytes from
 // the packet's start and `piece` bytes from byte src2 of the packet. A copied packet (fs == 0) is one span, its caplen.
+// <true>: `gap` bytes lie between the two spans in the output (8 in an IPv6 fragment), which the patch kernel writes.
 struct OutPacket
 {
-	uint32_t k, j, head, piece, src2, fs;
+	uint32_t k, j, head, piece, src2, fs, gap;
 	uint64_t pos;
 };
 
+template <bool k6>
 __device__ __forceinline__ OutPacket out_packet(const FrIn& p, const Plan* s_plan, const uint32_t* s_cp,
                                                 const uint64_t* s_bp, uint32_t r)
 {
@@ -401,17 +553,26 @@ __device__ __forceinline__ OutPacket out_packet(const FrIn& p, const Plan* s_pla
 	x.pos = s_bp[x.k];
 	if (pl.disp == PCPPX_FRAG_SPLIT)
 	{
-		x.fs = frag_fs(p, pl.hdr);
-		x.head = (uint32_t)pl.ip_off + pl.hdr;
+		if constexpr (k6)
+			split_shape<true>(p, pl, x.head, x.gap, x.fs);
+		else
+		{
+			x.fs = frag_fs(p, pl.hdr);
+			x.head = (uint32_t)pl.ip_off + pl.hdr;
+		}
 		const uint32_t done = x.j * x.fs;  // < pay
 		x.piece = pl.pay - done < x.fs ? pl.pay - done : x.fs;
 		x.src2 = x.head + done;
-		x.pos += (uint64_t)x.j * (x.head + x.fs);  // the fragments before it are full
+		if constexpr (k6)
+			x.pos += (uint64_t)x.j * (x.head + x.gap + x.fs);
+		else
+			x.pos += (uint64_t)x.j * (x.head + x.fs);  // the fragments before it are full
 	}
 	return x;
 }
 
-__global__ __launch_bounds__(kFrThreads) void frag_emit_kernel(FrIn p, FrOut o, const Plan* __restrict__ plan,
+template <bool k6>
+__global__ __launch_bounds__(kFrThreads) void frag_emit_kernel(In<k6> p, FrOut o, const Plan* __restrict__ plan,
                                                                const uint64_t* __restrict__ base_cnt,
                                                                const uint64_t* __restrict__ base_bytes)
 {
@@ -425,7 +586,7 @@ __global__ __launch_bounds__(kFrThreads) void frag_emit_kernel(FrIn p, FrOut o, 
 	__shared__ uint64_t s_sa[kFrWaves][64];
 	if (o.totals[PCPPX_FRAG_OVERFLOW] != 0)  // all or nothing: the same word for every block
 		return;
-	block_prefix(p, plan, s_plan, s_cp, s_bp, s_tc, s_tb);
+	block_prefix<k6>(p, plan, s_plan, s_cp, s_bp, s_tc, s_tb);
 	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 	const uint64_t first = tile_first(kFragBlockPk, 0);
 #pragma unroll 1
@@ -449,7 +610,7 @@ __global__ __launch_bounds__(kFrThreads) void frag_emit_kernel(FrIn p, FrOut o, 
 	{
 		const bool live = t0 + lane < total;
 		const uint32_t r = live ? t0 + lane : total - 1;
-		OutPacket x = out_packet(p, s_plan, s_cp, s_bp, r);
+		OutPacket x = out_packet<k6>(p, s_plan, s_cp, s_bp, r);
 		const uint64_t i = first + x.k;  // < n: it puts out a packet
 		const uint64_t off = p.offsets[i];
 		if (x.fs == 0)
@@ -459,7 +620,10 @@ __global__ __launch_bounds__(kFrThreads) void frag_emit_kernel(FrIn p, FrOut o, 
 		{
 			const uint64_t rank = rank0 + r;  // < OUT_PACKETS <= max_packets
 			o.offsets[rank] = pos;
-			o.caplens[rank] = x.head + x.piece;
+			if constexpr (k6)
+				o.caplens[rank] = x.head + x.gap + x.piece;
+			else
+				o.caplens[rank] = x.head + x.piece;
 			if (o.index != nullptr)
 				o.index[rank] = (uint32_t)i;
 			if (o.frag_no != nullptr)
@@ -471,12 +635,14 @@ __global__ __launch_bounds__(kFrThreads) void frag_emit_kernel(FrIn p, FrOut o, 
 		const bool pc = live && x.piece != 0;
 		if (__ballot(pc) == 0)
 			continue;
-		copy_spans(sbase, dbase, lane, pc, off + x.src2 + sal, pos + x.head + dal, pc ? x.piece : 0u, s_ccp[w], s_dq[w],
-		           s_sa[w]);
+		// <true>: the piece lands behind the gap; [pos + head, pos + head + gap) is in no span and so in no store here
+		const uint64_t q2 = k6 ? pos + x.head + x.gap + dal : pos + x.head + dal;
+		copy_spans(sbase, dbase, lane, pc, off + x.src2 + sal, q2, pc ? x.piece : 0u, s_ccp[w], s_dq[w], s_sa[w]);
 	}
 }
 
-__global__ __launch_bounds__(kFrThreads) void frag_patch_kernel(FrIn p, FrOut o, const Plan* __restrict__ plan,
+template <bool k6>
+__global__ __launch_bounds__(kFrThreads) void frag_patch_kernel(In<k6> p, FrOut o, const Plan* __restrict__ plan,
                                                                 const uint64_t* __restrict__ base_bytes,
                                                                 const uint32_t* __restrict__ bsplit)
 {
@@ -487,16 +653,58 @@ __global__ __launch_bounds__(kFrThreads) void frag_patch_kernel(FrIn p, FrOut o,
 	__shared__ uint64_t s_tb[kFrTiles];
 	if (o.totals[PCPPX_FRAG_OVERFLOW] != 0 || bsplit[blockIdx.x] == 0)  // the same for the whole block
 		return;
-	block_prefix(p, plan, s_plan, s_cp, s_bp, s_tc, s_tb);
+	block_prefix<k6>(p, plan, s_plan, s_cp, s_bp, s_tc, s_tb);
 	const uint32_t total = s_cp[kFragBlockPk];
 	const uint64_t pos0 = base_bytes[blockIdx.x];
 	for (uint32_t r = threadIdx.x; r < total; r += kFrThreads)
 	{
-		const OutPacket x = out_packet(p, s_plan, s_cp, s_bp, r);
+		const OutPacket x = out_packet<k6>(p, s_plan, s_cp, s_bp, r);
 		const Plan pl = s_plan[x.k];
 		if (pl.disp != PCPPX_FRAG_SPLIT)
 			continue;
 		const uint32_t c = s_cp[x.k + 1] - s_cp[x.k];
+		if constexpr (k6)
+		{
+			if ((pl.sum & kPlanV6) != 0)
+			{
+				// the fragment header (the gap, all 8 bytes), the next-header byte that now names it and the payload
+				// length; the old next-header value from the source packet, the id from the caller
+				const uint64_t i = tile_first(kFragBlockPk, 0) + x.k;
+				const uint32_t nh_at = (uint32_t)pl.ip_off + (pl.sum & 0xFFFFu);
+				const uint8_t nh_old = p.data[p.offsets[i] + nh_at];
+				const uint32_t id = p.ids != nullptr ? p.ids[i] : p.id_base + (uint32_t)i;
+				const uint32_t word = (x.j * x.fs) | (x.j + 1 < c ? 1u : 0u);
+				const uint32_t plen = (uint32_t)pl.hdr6 - kV6Fixed + kV6FragHdr + x.piece;  // < hdr + pay <= 65535
+				uint8_t* d = o.data + pos0 + x.pos;
+				uint8_t* fh = d + x.head;
+				fh[0] = nh_old;
+				fh[1] = 0;
+				fh[2] = (uint8_t)(word >> 8);
+				fh[3] = (uint8_t)word;
+				fh[4] = (uint8_t)(id >> 24);
+				fh[5] = (uint8_t)(id >> 16);
+				fh[6] = (uint8_t)(id >> 8);
+				fh[7] = (uint8_t)id;
+				d[nh_at] = 44;
+				d[pl.ip_off + 4] = (uint8_t)(plen >> 8);
+				d[pl.ip_off + 5] = (uint8_t)plen;
+				// the type field ahead of every VLAN layer in front of the IPv6 header, as EthLayer's, VlanLayer's and
+				// SllLayer's computeCalculateFields leave it: 0x8100, an 802.1ad tag's 0x88A8 too
+				const pcppx_layer* lay = p.layers + i * p.ml;
+				uint32_t nl = p.n_layers[i * p.nl_stride];
+				nl = nl < p.ml ? nl : p.ml;
+				for (uint32_t k = 0; k + 1 < nl && lay[k].proto != kProtoIPv6; ++k)
+				{
+					const pcppx_layer next = lay[k + 1];
+					if (next.proto == kProtoVlan && next.offset >= 2 && next.offset <= pl.ip_off)
+					{
+						d[next.offset - 2] = 0x81;
+						d[next.offset - 1] = 0x00;
+					}
+				}
+				continue;
+			}
+		}
 		const uint32_t tot_len = (uint32_t)pl.hdr + x.piece;  // <= hdr + pay <= 65535
 		const uint32_t word = ((x.j * x.fs) >> 3) | (x.j + 1 < c ? 0x2000u : 0u);
 		uint32_t sum = pl.sum + tot_len + word;
@@ -525,9 +733,10 @@ uint64_t frag_scratch_bytes(uint32_t n)
 }
 
 int launch_frag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
-                uint32_t nl_stride, const pcppx_frag_spec* spec, const pcppx_fragmented* out, void* scratch,
+                uint32_t nl_stride, const pcppx_frag6_spec* spec, const pcppx_fragmented* out, void* scratch,
                 hipStream_t stream)
 {
+	const bool k6 = (spec->families & PCPPX_FRAG_FAM_V6) != 0;
 	const uint32_t g = frag_blocks(b->n);
 	// bcnt, bbytes, base_cnt, base_bytes [g each, 64-bit] | five sums [g each, 32-bit] | plan[n]; 52 g + 12 n bytes
 	uint64_t* bcnt = static_cast<uint64_t*>(scratch);
@@ -540,11 +749,28 @@ int launch_frag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, co
 		     n_layers, nl_stride,  spec->keep,     spec->frag_size, spec->mtu, spec->copy_rest, spec->honor_df };
 	FrOut o{ out->data,    out->data_cap, out->offsets,     out->caplens,     out->index,
 		     out->frag_no, out->counts,   out->disposition, out->max_packets, out->totals };
-	hipLaunchKernelGGL(frag_plan_kernel, dim3(g), dim3(kFrThreads), 0, stream, in, plan, bcnt, bbytes, bsums);
+	FrIn6 in6{};
+	static_cast<FrIn&>(in6) = in;
+	in6.families = spec->families;
+	in6.id_base = spec->id_base;
+	in6.ids = spec->ids;
+	const dim3 grid(g), block(kFrThreads);
+	if (k6)
+		hipLaunchKernelGGL(frag_plan_kernel<true>, grid, block, 0, stream, in6, plan, bcnt, bbytes, bsums);
+	else
+		hipLaunchKernelGGL(frag_plan_kernel<false>, grid, block, 0, stream, in, plan, bcnt, bbytes, bsums);
 	hipLaunchKernelGGL(frag_base_kernel, dim3(1), dim3(64), 0, stream, g, bcnt, bbytes, bsums, base_cnt, base_bytes, o);
-	hipLaunchKernelGGL(frag_emit_kernel, dim3(g), dim3(kFrThreads), 0, stream, in, o, plan, base_cnt, base_bytes);
+	if (k6)
+		hipLaunchKernelGGL(frag_emit_kernel<true>, grid, block, 0, stream, in6, o, plan, base_cnt, base_bytes);
+	else
+		hipLaunchKernelGGL(frag_emit_kernel<false>, grid, block, 0, stream, in, o, plan, base_cnt, base_bytes);
 	if (out->data != nullptr)  // bsums' first row: the blocks' split packets
-		hipLaunchKernelGGL(frag_patch_kernel, dim3(g), dim3(kFrThreads), 0, stream, in, o, plan, base_bytes, bsums);
+	{
+		if (k6)
+			hipLaunchKernelGGL(frag_patch_kernel<true>, grid, block, 0, stream, in6, o, plan, base_bytes, bsums);
+		else
+			hipLaunchKernelGGL(frag_patch_kernel<false>, grid, block, 0, stream, in, o, plan, base_bytes, bsums);
+	}
 	return check_launch("frag", stream);
 }
 }  // namespace pcppx

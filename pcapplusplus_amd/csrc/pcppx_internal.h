@@ -85,15 +85,16 @@ uint64_t tcpstream_scratch_bytes(uint32_t n, uint32_t max_segments);
 int launch_tcpstream(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0,
                      uint32_t rec_stride, const pcppx_reasm_info* info, const pcppx_tcpstream_spec* spec,
                      const pcppx_tcpstreams* out, void* scratch, hipStream_t stream);
-// pcppx_frag_device (pcppx_frag.hip): three or four launches on `stream` (plan, bases, emit; with out->data the header
-// patch). scratch: frag_scratch_bytes(n) bytes (include/pcppx.h gives the formula); one block takes kFragBlockPk source
+// pcppx_frag_device / pcppx_frag6_device (pcppx_frag.hip): three or four launches on `stream` (plan, bases, emit; with
+// out->data the header patch). spec->families = V4 alone (pcppx_frag_device's spec arrives so): frag's kernels.
+// scratch: frag_scratch_bytes(n) bytes (include/pcppx.h gives the formula); one block takes kFragBlockPk source
 // packets and puts out all of their output packets; n_layers / nl_stride as for launch_defrag. Arguments are checked
 // by the caller; n > 0.
 constexpr uint32_t kFragBlockPk = 1024;
 uint32_t frag_blocks(uint32_t n);
 uint64_t frag_scratch_bytes(uint32_t n);
 int launch_frag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
-                uint32_t nl_stride, const pcppx_frag_spec* spec, const pcppx_fragmented* out, void* scratch,
+                uint32_t nl_stride, const pcppx_frag6_spec* spec, const pcppx_fragmented* out, void* scratch,
                 hipStream_t stream);
 // pcppx_tlsfp_device (pcppx_tlsfp.hip): three launches on `stream` (plan, bases, emit). scratch: tlsfp_scratch_bytes(n)
 // bytes (include/pcppx.h gives the formula); one block takes kTlsfpBlockPk source packets and writes their records;

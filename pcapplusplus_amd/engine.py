@@ -266,6 +266,22 @@ class Engine:
         abi.check(self.lib.pcppx_frag_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_frag_device")
 
+    def frag6_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int,
+                     spec: abi.Frag6Spec, out_offsets, out_caplens, totals, max_packets: int, out_data=None,
+                     data_cap: int = 0, out_index=None, out_frag_no=None, counts=None, disposition=None,
+                     stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
+        """Queue pcppx_frag6_device over device tensors: frag_device for the families spec.families names (the IPv6
+        packets are split too, with the fragment ids of spec.ids / spec.id_base). The arguments are frag_device's."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.Fragmented(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+                             opt(out_frag_no), opt(counts), opt(disposition), max_packets, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_frag6_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_frag6_device")
+
     def tlsfp_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int,
                      spec: abi.TlsfpSpec, recs, totals, max_recs: int, text=None, text_cap: int = 0, disposition=None,
                      stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
@@ -792,6 +808,18 @@ def defrag_on_device(eng: Engine, batch: PacketBatch, records, layers, info, pas
     return out, index, first, frags, dispo, tot
 
 
+def frag6_on_device(eng: Engine, batch: PacketBatch, records, layers, frag_size: int = 0, mtu: int = 0,
+                    families: int = abi.FRAG_FAM_V4 | abi.FRAG_FAM_V6, ids=None, id_base: int = 0, keep=None,
+                    copy_rest: bool = True, honor_df: bool = False, data_cap: int | None = None,
+                    max_packets: int | None = None, index_only: bool = False, device: str = "cuda:0"):
+    """frag_on_device through pcppx_frag6_device: the packets of the families named (abi.FRAG_FAM_* bits) are split,
+    the IPv6 ones too. ids: one u32 fragment id per source packet (None: id_base + i). The other arguments and the
+    results are frag_on_device's."""
+    return _frag_on_device(eng, batch, records, layers, frag_size=frag_size, mtu=mtu, keep=keep, copy_rest=copy_rest,
+                           honor_df=honor_df, data_cap=data_cap, max_packets=max_packets, index_only=index_only,
+                           device=device, families=families, ids=ids, id_base=id_base)
+
+
 def frag_on_device(eng: Engine, batch: PacketBatch, records, layers, frag_size: int = 0, mtu: int = 0, keep=None,
                    copy_rest: bool = True, honor_df: bool = False, data_cap: int | None = None,
                    max_packets: int | None = None, index_only: bool = False, device: str = "cuda:0"):
@@ -805,6 +833,14 @@ def frag_on_device(eng: Engine, batch: PacketBatch, records, layers, frag_size: 
     / max_packets default to what an index-only call says the output needs. All or nothing: when totals["overflow"] is
     set the returned batch and columns are empty. timestamps_ns follow the packets through index; a fragment's frame
     length is its caplen, a copied packet keeps its own."""
+    return _frag_on_device(eng, batch, records, layers, frag_size=frag_size, mtu=mtu, keep=keep, copy_rest=copy_rest,
+                           honor_df=honor_df, data_cap=data_cap, max_packets=max_packets, index_only=index_only,
+                           device=device, families=None, ids=None, id_base=0)
+
+
+def _frag_on_device(eng: Engine, batch: PacketBatch, records, layers, *, frag_size, mtu, keep, copy_rest, honor_df,
+                    data_cap, max_packets, index_only, device, families, ids, id_base):
+    """frag_on_device (families None: pcppx_frag_device) and frag6_on_device (the abi.FRAG_FAM_* bits, ids / id_base)."""
     import torch
 
     n = batch.n
@@ -818,16 +854,23 @@ def frag_on_device(eng: Engine, batch: PacketBatch, records, layers, frag_size: 
     data, offsets, caplens = to_device(batch, device)
     rec_t, lay_t = up(pad(rec)), up(pad(lay.reshape(-1)))
     keep_t = None if keep is None else up(pad(np.ascontiguousarray(keep).astype(np.uint8)))
-    spec = abi.make_frag_spec(frag_size, mtu, None if keep_t is None else abi.ptr(keep_t), copy_rest, honor_df)
+    keep_p = None if keep_t is None else abi.ptr(keep_t)
+    if families is None:
+        frag_call, spec = eng.frag_device, abi.make_frag_spec(frag_size, mtu, keep_p, copy_rest, honor_df)
+    else:
+        ids_t = None if ids is None else up(pad(np.ascontiguousarray(ids).astype(np.uint32)))
+        frag_call = eng.frag6_device
+        spec = abi.make_frag6_spec(frag_size, mtu, families, None if ids_t is None else abi.ptr(ids_t), id_base,
+                                   keep_p, copy_rest, honor_df)
     is_brief = rec.dtype.itemsize == abi.BRIEF_DTYPE.itemsize
     st = torch.cuda.current_stream(device).cuda_stream
     totals = torch.empty(abi.FRAG_TOTALS, dtype=torch.int64, device=device)
     one64, one32 = torch.empty(1, dtype=torch.int64, device=device), torch.empty(1, dtype=torch.int32, device=device)
 
     def call(out_off, out_cap, mp, out_data=None, cap=0, idx=None, no=None, cnt=None, disp=None):
-        eng.frag_device(data, offsets, caplens, n, batch.linktype, lay_t, ml, spec, out_off, out_cap, totals, mp,
-                        out_data, cap, idx, no, cnt, disp, st, summary=None if is_brief else rec_t,
-                        brief=rec_t if is_brief else None)
+        frag_call(data, offsets, caplens, n, batch.linktype, lay_t, ml, spec, out_off, out_cap, totals, mp,
+                  out_data, cap, idx, no, cnt, disp, st, summary=None if is_brief else rec_t,
+                  brief=rec_t if is_brief else None)
         torch.cuda.synchronize(device)
         return abi.frag_totals_dict(totals.cpu().numpy().view(np.uint64))
 

@@ -142,21 +142,23 @@ def fragment(batch: PacketBatch, frag_size: int, select=None) -> PacketBatch:
 
 
 _V6_MAX_EXT = 8  # extensions locate_ipv6 walks before it gives a packet up
+_L2_LEN = {abi.LINKTYPE_ETHERNET: 14, abi.LINKTYPE_LINUX_SLL: 16}  # the type field is the header's last two bytes
 
 
 def locate_ipv6(batch: PacketBatch):
-    """(is_v6, ip_off, hdr, payload, nh_at, fragmented) per packet: the IPv6 header behind Ethernet and up to two VLAN
-    tags, the length of its fixed header and extensions (parseExtensions, Packet++/src/IPv6Layer.cpp:79-147: types 0,
+    """(is_v6, ip_off, hdr, payload, nh_at, fragmented) per packet: the IPv6 header behind Ethernet (or a Linux cooked
+    header) and up to two VLAN tags, the length of its fixed header and extensions (parseExtensions,
+    Packet++/src/IPv6Layer.cpp:79-147: types 0,
     43 and 60 are (len8 + 1) * 8 bytes, 44 is 8, 51 is (len8 + 2) * 4), the IP payload's length as the reference's
     layer has it (min(captured, payloadLength + hdr) - hdr, IPv6Layer.cpp:37-39), the packet offset of the next-header
     byte of the last extension (of the fixed header without one) and whether a fragment header is among them. is_v6 is
     False where there is none, where the extensions are cut short or more than _V6_MAX_EXT, or where the link type is
-    not Ethernet."""
+    neither."""
     n = batch.n
     off = batch.offsets.astype(np.int64)
     cap = batch.caplens.astype(np.int64)
     zero = np.zeros(n, np.int64)
-    if n == 0 or batch.linktype != abi.LINKTYPE_ETHERNET:
+    if n == 0 or batch.linktype not in _L2_LEN:
         return np.zeros(n, bool), zero, zero.copy(), zero.copy(), zero.copy(), np.zeros(n, bool)
     d = batch.data
     last = max(len(d) - 1, 0)
@@ -167,8 +169,8 @@ def locate_ipv6(batch: PacketBatch):
     def be16(pos):
         return (u8(pos) << 8) | u8(pos + 1)
 
-    ip_off = np.full(n, 14, np.int64)
-    et = be16(12)
+    ip_off = np.full(n, _L2_LEN[batch.linktype], np.int64)
+    et = be16(ip_off - 2)
     for _ in range(2):
         tagged = (et == 0x8100) | (et == 0x88A8)
         et = np.where(tagged, be16(ip_off + 2), et)
@@ -201,7 +203,9 @@ def fragment6(batch: PacketBatch, frag_size: int, ids, select=None) -> PacketBat
     (IPv6FragmentationHeader, added behind the last extension: it takes over that extension's next-header value, and
     the extension -- the fixed header without one -- now names type 44), then payload bytes
     [j * size, min((j + 1) * size, payload)); the payload length is rewritten (computeCalculateFields) and a trailer
-    behind the IP payload is dropped. ids: one 32-bit fragment id per source packet (IPFragUtil draws a random one per
+    behind the IP payload is dropped; the type field ahead of every VLAN tag becomes 0x8100 (computeCalculateFields of
+    the layer in front of it: an 802.1ad tag's 0x88A8 is renamed). ids: one 32-bit fragment id per source packet
+    (IPFragUtil draws a random one per
     packet; here the caller says, so that the result is a function of the inputs). select, the meta columns,
     timestamps_ns and frame_lens are fragment()'s. IPv4 packets are copied: fragment() splits those."""
     fs = frag_size // 8 * 8
@@ -248,6 +252,10 @@ def fragment6(batch: PacketBatch, frag_size: int, ids, select=None) -> PacketBat
         plen = hdr[s] - 40 + 8 + piece[f]
         ip = base + ip_off[s]
         data[ip + 4], data[ip + 5] = (plen >> 8).astype(np.uint8), (plen & 255).astype(np.uint8)
+        l2 = _L2_LEN[batch.linktype]
+        for t in range(2):
+            at = (base + l2 - 2 + 4 * t)[(ip_off[s] - l2) // 4 > t]
+            data[at], data[at + 1] = 0x81, 0x00
     out = PacketBatch(np.concatenate([data, np.zeros(1, np.uint8)]), out_off.astype(np.uint64),
                       out_len.astype(np.uint32), batch.linktype)
     if batch.timestamps_ns is not None:

@@ -2,7 +2,7 @@
 keeping every packet.
 
   python tools/bench_defrag.py [packets] [launches] [percentages, e.g. 0,1,20] [--families 4|6|46[,...]] [--entry6]
-                               [--base-lib path/to/an/older/libpcppx.so]
+                               [--base-lib path/to/an/older/libpcppx.so] [--device-input]
 
 Workload: config-3 IMIX (10M packets by default) with 0 %, 1 % and 20 % of its IPv4 packets fragmented at 576 payload
 bytes (pcapplusplus_amd.frag: IPFragUtil's rule), resident in HBM, parsed once with the reassembly front end
@@ -12,8 +12,10 @@ nothing but fragments) and the power of two at or above the batch's candidates.
 --families names what is timed, one variant per entry of a comma list: 4 (the default: the numbers stay comparable with
 the earlier ones) is pcppx_defrag_device, and with --entry6 also pcppx_defrag6_device with families = V4; 6 and 46 are
 pcppx_defrag6_device with families = V6 and V4 | V6. With a 6 or 46 in the list the same share of the batch's IPv6
-packets is fragmented too (frag.fragment6, the ids the packet numbers). --base-lib adds pcppx_defrag_device of another
-build of the library (the parent commit's, say) as a variant, with a context of its own in the same process.
+packets is fragmented too (frag.fragment6, the ids the packet numbers; with --device-input by pcppx_frag6_device with
+families = V6 over the same packets and ids instead, which gives the same batch without the host pass). --base-lib
+adds pcppx_defrag_device of another build of the library (the parent commit's, say) as a variant, with a context of
+its own in the same process.
 Yardstick: pcppx_select_device with a keep-all mask over the same batch (it moves the same bytes but for the dropped
 fragment headers), timed in the same process in rounds that alternate with the variants' launches, `launches` (>= 50)
 launches of each between HIP events on the launch stream.
@@ -32,7 +34,7 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 
 from pcapplusplus_amd import abi, frag, synth  # noqa: E402
-from pcapplusplus_amd.engine import Engine, to_device  # noqa: E402
+from pcapplusplus_amd.engine import Engine, frag6_on_device, parse_on_device, to_device  # noqa: E402
 
 
 def option(argv: list, name: str, default=None):
@@ -48,6 +50,9 @@ argv = list(sys.argv[1:])
 entry6 = "--entry6" in argv
 if entry6:
     argv.remove("--entry6")
+device_input = "--device-input" in argv
+if device_input:
+    argv.remove("--device-input")
 families = option(argv, "--families", "4").split(",")
 base_lib = option(argv, "--base-lib")
 if not families or any(f not in ("4", "6", "46") for f in families):
@@ -96,7 +101,14 @@ for pct in pcts:
     b = frag.fragment(base, 576, select=rng.random(base.n) < pct / 100) if pct else base
     if pct and both:  # a packet's fragments share its number, which is its fragment id
         chosen = (rng.random(base.n) < pct / 100)[b.meta["frag_src"]]
-        b = frag.fragment6(b, 576, b.meta["frag_src"], select=chosen)
+        if device_input:
+            opts = abi.make_opts(0, 8, False, ML)
+            b, *_ = frag6_on_device(eng, b, *parse_on_device(eng, b, opts), frag_size=576, families=abi.FRAG_FAM_V6,
+                                    ids=b.meta["frag_src"], keep=chosen)
+            b.data = np.concatenate([b.data, np.zeros(1, np.uint8)])
+            torch.cuda.empty_cache()
+        else:
+            b = frag.fragment6(b, 576, b.meta["frag_src"], select=chosen)
     n = b.n
     print(f"{pct} % fragmented: {n} packets", file=sys.stderr, flush=True)
     total = int(b.caplens.sum(dtype=np.uint64))
@@ -173,7 +185,8 @@ for pct in pcts:
     del data, offsets, caplens, summary, layers, info, out_data, out_off, out_cap, out_idx, out_first, out_frags, disp
     torch.cuda.empty_cache()
 print(json.dumps({"kernel": "defrag (collect + verdict + count + bases + place + merge + patch)",
-                  "families": families, "ipv6_fragmented": both, "base_lib": base_lib, "source_packets": n0,
+                  "families": families, "ipv6_fragmented": both, "device_input": device_input, "base_lib": base_lib,
+                  "source_packets": n0,
                   "frag_size": 576, "launches_per_case": ROUNDS * per_round, "cases": results}))
 if base_eng is not None:
     base_eng.close()
