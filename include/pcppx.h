@@ -159,11 +159,17 @@ typedef struct pcppx_opts {
                                   96 B take the generic walk. Checksum launches: as DEFAULT */
 
 /* pcppx_records.layers layouts (pcppx_opts.layout). Both hold the same pcppx_layer entries, bit for bit:
- *   FIXED:  packet i's layer k is layers[i * max_layers + k], k < min(n_layers, max_layers); entries past
- *           n_layers are unspecified.
- *   PACKED: only the chain's entries are written, densely per 64-packet tile: the entries of tile t (packets
- *           64t .. 64t+63) start at layers[64 * t * max_layers], and packet i's entries follow those of the packets
+ *   FIXED:  packet i's layer k is layers[i * max_layers + k], k < min(n_layers, max_layers); the entries of a row past
+ *           its chain are unspecified (the fast path stores whole rows, zero past the chain; the generic walk stores
+ *           the chain alone: a reused buffer keeps what it held there). Nothing is written outside rows 0 .. n-1.
+ *   PACKED: the chains densely per 64-packet tile: the entries of tile t (packets 64t .. 64t+63) start at
+ *           layers[64 * t * max_layers], and packet i's entries follow those of the packets
  *           before it in its tile: layers[64 * t * max_layers + sum_{64t <= j < i} min(n_layers_j, max_layers) + k].
+ *           A tile writes only inside its own region, entries [64 * t * max_layers, min(64 * (t + 1), n) * max_layers):
+ *           the run of its first total_t = sum_j min(n_layers_j, max_layers) entries holds the chains, and the rest of
+ *           the region is unspecified (a packet off the fast path first stores its chain at its FIXED slot inside the
+ *           region, from where the run is packed: such entries at or past the run keep those values). Nothing is
+ *           written at or past layers[n * max_layers].
  *           The buffer is sized as for FIXED (n * max_layers entries); the summary or the brief is required (its
  *           n_layers decode the positions: pcppx_unpack_layers[_brief] below, pcppx::unpackLayers in include/pcppx.hpp). The write
  *           traffic is the chain, not max_layers rows per packet. max_layers <= PCPPX_PACKED_MAX_LAYERS. Device parse
@@ -218,7 +224,11 @@ typedef struct pcppx_tuple {
                                  not classify -- as pcppx_packet_stats.needs_host_count */
 #define PCPPX_PROTO_STATS 16  /* words (11-15 are zero) */
 
-/* Output arrays (same memory space as the batch for the _device call, host for the _host call). */
+/* Output arrays (same memory space as the batch for the _device call, host for the _host call). The device writes them
+ * with vector stores, so every array must have its record's natural alignment: 16 bytes for summary, brief, tuples
+ * and pcppx_reasm_info, 8 bytes for layers and proto_stats, 4 bytes for flow_keys. Only entries 0 .. n-1 of an array
+ * (n * max_layers entries of layers) are written, every byte of them except the unspecified layer entries of
+ * pcppx_opts.layout; proto_stats is accumulated. */
 typedef struct pcppx_records {
 	pcppx_summary* summary; /* n entries, or NULL when `brief` is set; may also be NULL on the device path when max_layers
 	                           is 0 and one of tuples / flow_keys / proto_stats is set (e.g. a flow table's launch: dense
