@@ -302,7 +302,14 @@ PCPPX_API int pcppx_parse_batch_host(pcppx_ctx* ctx, const pcppx_batch* batch, c
  * empty slot — flow key 0 (non-5-tuple packets, PacketUtils.cpp:141-148) is counted in stats[0] (packets) /
  * stats[1] (bytes) instead, and packets whose region had no free slot in stats[2]. Counts accumulate across
  * calls; calls on one context are ordered (they share its scratch). HBM scratch held by the context: record
- * queues of 16 B x min(n, 2^24) x ~1.25 (grown in stream order, freed by pcppx_close). */
+ * queues of 16 B x min(n, 2^24) x ~1.25 (grown in stream order, freed by pcppx_close).
+ * stats is three words: key-0 packets, key-0 bytes, lost packets; nothing behind stats[2] is touched.
+ * Slots with key 0 keep zero counts: packets[s] == bytes[s] == 0 wherever keys[s] == 0.
+ * caplens[i] <= PCPPX_MAX_CAPLEN is required wherever the key is non-zero (a launch carries a flow's bytes in a
+ * 40-bit field: 2^24 - 1 packets of 65535 B at most). Records of a parse satisfy it: OVERSIZE and BAD_DESC packets
+ * have key 0, and key-0 bytes are summed in 64 bits whatever the caplen. With larger values the per-flow counts are
+ * unspecified.
+ * A call of more than 2^24 - 1 packets is processed in consecutive launches with the same result. */
 /* The same over the dense key column a parse wrote (pcppx_records.flow_keys): keys_in[i] = hash5 of packet i. */
 PCPPX_API int pcppx_flow_count_keys_device(pcppx_ctx* ctx, const uint32_t* keys_in, const uint32_t* caplens, uint32_t n,
                                            uint32_t* keys, uint64_t* packets, uint64_t* bytes, uint32_t capacity,
@@ -318,7 +325,9 @@ PCPPX_API int pcppx_flow_count_device(pcppx_ctx* ctx, const pcppx_summary* summa
  * Packet order is the worker's receive order: packet i of the batch has sequence number seq_base + i,
  * and a packet matches if it matches on its own or an earlier packet of the same 5-tuple flow matched.
  * The flow table (flow_keys / flow_first, `capacity` slots, power of two, zero-initialised) persists
- * across batches like the worker's m_FlowTable. */
+ * across batches like the worker's m_FlowTable. A used slot holds flow_keys[s] = 1 << 32 | hash5 and flow_first[s] =
+ * ~(sequence number of the flow's first packet that matched on its own); seq_base + n must stay below 2^64 - 1
+ * (sequence number 2^64 - 1 would be stored as 0, the empty value). */
 typedef struct pcppx_match_spec {
 	uint32_t src_ip;   /* IPv4Address::toInt() (network byte order in memory); 0 = any */
 	uint32_t dst_ip;   /* 0 = any */

@@ -302,6 +302,7 @@ def test_gpu_flow_hash_symmetry_and_flow_table(engine):
     torch.cuda.synchronize()
     k = keys.cpu().numpy().view(np.uint32)
     used = k != 0
+    assert len(np.unique(k[used])) == int(used.sum())  # no key stored in two slots
     got = dict(zip(k[used].tolist(), zip(pk.cpu().numpy()[used].tolist(), by.cpu().numpy()[used].tolist())))
     uniq, inv = np.unique(s["hash5"], return_inverse=True)
     cnt = np.bincount(inv)
@@ -326,6 +327,7 @@ def _device_flow_table(engine, s, caplens, n, cap, calls=1):
     torch.cuda.synchronize()
     k = keys.cpu().numpy().view(np.uint32)
     used = k != 0
+    assert len(np.unique(k[used])) == int(used.sum())  # no key stored in two slots
     got = dict(zip(k[used].tolist(), zip(pk.cpu().numpy()[used].tolist(), by.cpu().numpy()[used].tolist())))
     return got, st.cpu().numpy()
 
@@ -405,6 +407,7 @@ def test_gpu_flow_keys_column(engine):
         torch.cuda.synchronize()
         k = keys.cpu().numpy().view(np.uint32)
         used = k != 0  # slot positions depend on the claim order: compare by key
+        assert len(np.unique(k[used])) == int(used.sum())  # no key stored in two slots
         tabs.append((dict(zip(k[used].tolist(), zip(pk.cpu().numpy()[used].tolist(), by.cpu().numpy()[used].tolist()))),
                      stt.cpu().numpy().tolist()))
     assert tabs[0] == tabs[1] and len(tabs[0][0]) > 50_000
@@ -561,6 +564,7 @@ def test_gpu_config4_full_size_flow_table(engine, shard_range):
     torch.cuda.synchronize()
     k = keys.cpu().numpy().view(np.uint32)
     used = k != 0
+    assert len(np.unique(k[used])) == int(used.sum())  # no key stored in two slots
     got = dict(zip(k[used].tolist(), zip(pk.cpu().numpy()[used].tolist(), by.cpu().numpy()[used].tolist())))
     hk = fk.cpu().numpy().view(np.uint32)
     pstats = ps.cpu().numpy()
