@@ -1574,6 +1574,169 @@ PCPPX_API int pcppx_http_device(pcppx_ctx* ctx, const pcppx_batch* batch, const 
 PCPPX_API int pcppx_http_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                    const pcppx_http_spec* spec, pcppx_http_out* out);
 
+/* ---- ssl: the SSL/TLS records, the hellos and the SNI of the SSL packets of a device batch ----
+ * What SSLStatsCollector::collectStats reads of a packet (Examples/SSLAnalyzer/SSLStatsCollector.h:141-401), for packets
+ * that sit in HBM: per SSL packet one message record (the TCP payload size, the ports, the record-type mix), per
+ * ClientHello / ServerHello one record (the versions, the cipher suite, the counts, the SNI host name's place), and the
+ * host names back to back. Added within ABI 7: new symbols only (PCPPX_ABI_VERSION stays 7).
+ *
+ * Inputs: as http. A device batch and its FIXED records (max_layers >= 1, the same value as the parse used; the summary
+ * or, when it is NULL, the brief supplies flags and n_layers; PACKED and DENSE records are refused).
+ *
+ * Per packet i the first rule that applies decides (be16(x): the big-endian 16-bit word at byte x):
+ *   1 BAD_DESC. offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (the rule of select, steer, defrag, frag,
+ *     tlsfp, dns and http): the packet is never read.
+ *   2 Incomplete chain: HOST when flags has PCPPX_F_NEEDS_HOST_PROTO, OVERSIZE, BAD_DESC or DEPTH_OVERFLOW, or
+ *     n_layers > max_layers, or NEEDS_HOST_L7 is set with L7_SSL set or without L7_KNOWN. The analyzer walks every SSL
+ *     layer of the packet (SSLStatsCollector.h:319-375), so a chain the device did not record to its end is the host's
+ *     even when some SSL entries were recorded: stricter than tlsfp's rule 3, on purpose.
+ *   3 SSL entries. Every entry k < n_layers with proto == 18 (pcpp::SSL) that lies inside the packet (tlsfp's rule 2
+ *     bounds: data_len >= 5, hdr_len >= 5, hdr_len <= data_len, offset + data_len <= caplen) is followed, in order; its
+ *     record type is the byte at `offset`: 20 change-cipher-spec, 21 alert, 22 handshake, 23 application data
+ *     (SSLLayer.cpp:42-94). An entry that fails the bounds is skipped and never read. No followed entry: NONE.
+ *     Otherwise the packet is MSG and gets one message record. payload_len is the first followed entry's data_len
+ *     (tcpLayer->getLayerPayloadSize(), SSLStatsCollector.h:276). Ports: with k0 the first followed entry, entry k0 - 1
+ *     must have proto == 4 (pcpp::TCP) and offset + 4 <= caplen; then src_port = be16(offset) and dst_port =
+ *     be16(offset + 2). Otherwise (k0 == 0 included) both ports are 0 and PCPPX_SSL_NO_TCP is set. ssl_port is src_port
+ *     when SSLLayer::isSSLPort(src_port) holds (443, 261, 448, 465, 563, 614, 636, 989, 990, 992, 993, 994, 995;
+ *     SSLLayer.h:488-510), else dst_port (SSLStatsCollector.h:291-296). n_handshake, n_ccs, n_alert and n_appdata count
+ *     the followed entries by type, each saturating at 255; a followed entry of another type counts nowhere.
+ *   4 Messages of a handshake entry (SSLLayer.cpp:126-150, SSLHandshake.cpp:1287-1350, 2257-2262). R = hdr_len - 5,
+ *     cur = 0; loop: D = R - cur, stop when D < 4; the message starts at offset + 5 + cur. It is unknown, takes all of D
+ *     and ends the walk when (a) D >= 16 and either its first five bytes are zero or its byte 1 is >= 1, or (b) its
+ *     byte 0 is not one of 0, 1, 2, 4, 11, 12, 13, 14, 15, 16, 20: the default: of the switch at :1306-1332, whose
+ *     SSLUnknownMessage::getMessageLength() is the whole rest. Otherwise its type is byte 0, M = min(4 + be16(2), D)
+ *     and cur += M. The entry's ClientHello is the first message of type 1, its ServerHello the first of type 2
+ *     (getHandshakeMessageOfType<>, SSLStatsCollector.h:353-364). One entry can yield both; they are emitted in ascending
+ *     message offset, entry by entry. A kind that is not in spec->kinds is not emitted. (Case (b) is not in tlsfp's
+ *     rule 4: there a hello behind a message of type 8 or 22 is still found; the reference does not find it.) Below,
+ *     byte positions count from the message's first byte.
+ *   5 Shared pieces: the session id, the cipher count and the extension list are rules 5-6 of tlsfp, the same reference
+ *     functions. Field reads are bounded by D; the extension list is cut at M. n_ext is the number of extensions the
+ *     list yields. header_version = D < 6 ? 0 : be16(4). session_id_len = sid.
+ *   6 ClientHello record. version = header_version. n_ciphers is the count of tlsfp's rule 6; cipher is 0. SNI: the
+ *     first listed extension of type 0, with data position x and length L (SSLHandshake.cpp:1138-1160, 1551-1575).
+ *     None: no HAS_SNI. L == 0: HAS_SNI and an empty name (the reference returns "" and the analyzer counts it).
+ *     L >= 5: the name is the bytes [x + 5, min(x + 5 + be16(x + 3), x + L)); SNI_TRUNCATED when the min cut it.
+ *     1 <= L < 5: the reference reads the length word behind the extension and builds a string from an inverted range,
+ *     which is undefined; here HAS_SNI | SNI_MALFORMED is set and the name is empty: a deliberate departure, as tlsfp's
+ *     rule 7 has one.
+ *   7 ServerHello record. version is tlsfp's rule 7: of the first listed extension of type 43, len == 2 gives
+ *     be16(data), len == 3 with data[0] == 2 gives be16(data + 1); otherwise header_version (the len == 0 departure is
+ *     kept). cipher = 39 + sid + 2 > D ? 0 : be16(39 + sid), with HAS_CIPHER when it is in bounds (getCipherSuiteID's
+ *     isValid, SSLHandshake.cpp:1818-1830); whether the id is in the reference's name table is the host's concern.
+ *     n_ciphers is 0. There is no SNI.
+ *   8 Source bytes are read only inside followed SSL entries and the 4 port bytes, of in-bounds packets. */
+typedef struct pcppx_ssl_spec {
+	uint32_t max_msgs;   /* the SSL packets the call has room for; 0 = n (always enough) */
+	uint8_t kinds;       /* bit 0 PCPPX_SSL_KIND_CLIENT, bit 1 PCPPX_SSL_KIND_SERVER; 0 = message records only */
+	uint8_t reserved[3]; /* must be 0 */
+} pcppx_ssl_spec;
+
+#define PCPPX_SSL_KIND_CLIENT 1 /* pcppx_ssl_spec.kinds */
+#define PCPPX_SSL_KIND_SERVER 2
+
+#define PCPPX_SSL_CLIENT 1 /* pcppx_ssl_hello.kind */
+#define PCPPX_SSL_SERVER 2
+
+#define PCPPX_SSL_NO_TCP 1 /* pcppx_ssl_msg.flags: no TCP entry in front of the first followed SSL entry */
+
+/* pcppx_ssl_hello.flags */
+#define PCPPX_SSL_HAS_SNI 1       /* getExtensionOfType<SSLServerNameIndicationExtension>() finds one */
+#define PCPPX_SSL_SNI_TRUNCATED 2 /* the name's length word reaches past the extension: cut there */
+#define PCPPX_SSL_SNI_MALFORMED 4 /* 1 <= L < 5: the name is empty (rule 6) */
+#define PCPPX_SSL_HAS_CIPHER 8    /* a ServerHello's cipher word lies inside D */
+
+typedef struct pcppx_ssl_msg { /* 32 bytes per SSL packet, in source order */
+	uint64_t first_hello;  /* record number in out->hellos of its first hello record */
+	uint32_t index;        /* source packet number (strictly ascending) */
+	uint32_t name_bytes;   /* the bytes its hellos put into out->names */
+	uint16_t layer_offset; /* the first followed SSL entry's first byte, from the packet's first byte */
+	uint16_t payload_len;  /* that entry's data_len: the TCP layer's payload size */
+	uint16_t src_port;
+	uint16_t dst_port;
+	uint16_t ssl_port;     /* the port the analyzer's port table counts for a new flow */
+	uint8_t n_handshake;   /* followed entries of type 22, saturating at 255; likewise the next three */
+	uint8_t n_ccs;         /* type 20 */
+	uint8_t n_alert;       /* type 21 */
+	uint8_t n_appdata;     /* type 23 */
+	uint8_t n_hellos;      /* the hello records emitted for it */
+	uint8_t flags;         /* PCPPX_SSL_NO_TCP */
+} pcppx_ssl_msg;
+
+typedef struct pcppx_ssl_hello { /* 32 bytes per emitted hello: message by message, ascending msg_offset */
+	uint64_t name_pos;       /* where its host name lies (or, with names == NULL, would lie) in out->names */
+	uint32_t msg;            /* its message's record number in out->msgs */
+	uint16_t msg_offset;     /* the hello message's first byte, from the packet's first byte */
+	uint16_t name_len;       /* the host name's bytes; 0 without HAS_SNI */
+	uint16_t version;        /* ClientHello: header_version; ServerHello: rule 7 (getHandshakeVersion) */
+	uint16_t header_version;
+	uint16_t cipher;         /* ServerHello: getCipherSuiteID(); ClientHello: 0 */
+	uint16_t n_ciphers;      /* ClientHello: getCipherSuiteCount(); ServerHello: 0 */
+	uint16_t n_ext;          /* getExtensionCount() */
+	uint8_t kind;            /* PCPPX_SSL_CLIENT / PCPPX_SSL_SERVER */
+	uint8_t layer;           /* the entry k it came from */
+	uint8_t session_id_len;  /* getSessionIDLength() */
+	uint8_t flags;           /* PCPPX_SSL_HAS_SNI | SNI_TRUNCATED | SNI_MALFORMED | HAS_CIPHER */
+	uint8_t reserved[2];     /* written as 0 */
+} pcppx_ssl_hello;
+
+/* pcppx_ssl_out.disposition values */
+#define PCPPX_SSL_NONE 0     /* a whole chain without a followed SSL entry */
+#define PCPPX_SSL_MSG 1      /* a message record */
+#define PCPPX_SSL_HOST 2     /* the chain was not recorded to its end (rule 2) */
+#define PCPPX_SSL_BAD_DESC 3 /* the descriptor is out of bounds: never read */
+
+/* pcppx_ssl_out.totals words */
+#define PCPPX_SSL_MSGS 0
+#define PCPPX_SSL_HELLOS 1
+#define PCPPX_SSL_CLIENT_HELLOS 2
+#define PCPPX_SSL_SERVER_HELLOS 3
+#define PCPPX_SSL_NAME_BYTES 4
+#define PCPPX_SSL_HOST_N 5
+#define PCPPX_SSL_BAD_DESC_N 6
+#define PCPPX_SSL_PAYLOAD_BYTES 7 /* the sum of payload_len: SSLAnalyzer's amountOfSSLTraffic */
+#define PCPPX_SSL_ALERT_PKTS 8    /* messages with n_alert > 0 */
+#define PCPPX_SSL_APPDATA_PKTS 9  /* messages with n_appdata > 0 */
+/* word 10 is zero */
+#define PCPPX_SSL_OVERFLOW 11
+#define PCPPX_SSL_TOTALS 12
+
+typedef struct pcppx_ssl_out { /* device pointers; host pointers for pcppx_ssl_reference */
+	pcppx_ssl_msg* msgs;     /* max_msgs entries, in source order */
+	pcppx_ssl_hello* hellos; /* max_hellos entries: message by message */
+	uint8_t* names;          /* the host names back to back in record order, no terminator; NULL = positions only */
+	uint64_t names_cap;
+	uint8_t* disposition;    /* optional (NULL): n entries, PCPPX_SSL_* per source packet */
+	uint32_t max_msgs;
+	uint32_t max_hellos;
+	uint64_t* totals;        /* PCPPX_SSL_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_ssl_out;
+
+/* Capacity is all or nothing, as in http: OVERFLOW = 1 iff MSGS > out->max_msgs, or HELLOS > max_hellos, or
+ * names != NULL and NAME_BYTES > names_cap, or MSGS > spec->max_msgs (0 = n). Then only the totals are written (no
+ * record, no name byte, no disposition); they always hold the full would-be values. With names == NULL positions and
+ * lengths are still filled and the byte capacity is not applied. Sizing: a call with max_msgs = max_hellos = 0
+ * overflows (when there is an SSL packet) and gives MSGS, HELLOS and NAME_BYTES. The cost of a packet is linear in the
+ * bytes of its handshake entries.
+ * Source bytes are read only from in-bounds packets, inside followed SSL entries and the 4 port bytes. Nothing is
+ * written outside the first MSGS messages, the first HELLOS hello records, [0, NAME_BYTES) of names and the n
+ * dispositions. The output is a pure function of the inputs, bit-identical from run to run: positions come from counts
+ * and scans, and there are no atomics. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: a null ctx, batch, records, spec, out, totals, msgs or hellos; with n > 0 a null
+ * records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS; kinds above 3; a non-zero reserved byte. The work is queued on hip_stream and the call returns
+ * without waiting; calls on one context are ordered through its ssl scratch (a buffer and an event of their own, as
+ * http's). Scratch: with g = ceil(n / 1024) blocks, 64 g + 16 n bytes (per block ten 32-bit sums -- its messages, hello
+ * records, name bytes, client and server hellos, HOST and BAD_DESC packets, payload bytes, alert and app-data packets --
+ * and the 64-bit exclusive prefixes of the first three; per packet a 16-byte plan: its name bytes, its hello records,
+ * the disposition and what the totals sum); PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_ssl_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                               uint8_t max_layers, const pcppx_ssl_spec* spec, pcppx_ssl_out* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_ssl_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                  const pcppx_ssl_spec* spec, pcppx_ssl_out* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

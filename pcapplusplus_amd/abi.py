@@ -584,6 +584,73 @@ def http_reference(batch: Batch, records: Records, max_layers: int, spec: HttpSp
                                              C.byref(out)), "pcppx_http_reference")
 
 
+# pcppx_ssl_*: the SSL/TLS records, the hellos and the SNI of the SSL packets of a batch (include/pcppx.h, ssl)
+SSL_NONE, SSL_MSG, SSL_HOST, SSL_BAD_DESC = range(4)  # disposition
+SSL_CLIENT, SSL_SERVER = 1, 2                         # hello.kind
+SSL_KIND_CLIENT, SSL_KIND_SERVER = 1, 2               # spec.kinds bits
+SSL_NO_TCP = 1                                        # msg.flags
+SSL_HAS_SNI, SSL_SNI_TRUNCATED, SSL_SNI_MALFORMED, SSL_HAS_CIPHER = 1, 2, 4, 8  # hello.flags
+(SSL_MSGS, SSL_HELLOS, SSL_CLIENT_HELLOS, SSL_SERVER_HELLOS, SSL_NAME_BYTES, SSL_HOST_N, SSL_BAD_DESC_N,
+ SSL_PAYLOAD_BYTES, SSL_ALERT_PKTS, SSL_APPDATA_PKTS, _SSL_ZERO, SSL_OVERFLOW) = range(12)  # pcppx_ssl_out.totals
+SSL_TOTALS = 12
+SSL_TOTAL_NAMES = ("msgs", "hellos", "client_hellos", "server_hellos", "name_bytes", "host_n", "bad_desc",
+                   "payload_bytes", "alert_pkts", "appdata_pkts", "zero", "overflow")
+SSL_MSG_DTYPE = np.dtype(
+    [("first_hello", "<u8"), ("index", "<u4"), ("name_bytes", "<u4"), ("layer_offset", "<u2"), ("payload_len", "<u2"),
+     ("src_port", "<u2"), ("dst_port", "<u2"), ("ssl_port", "<u2"), ("n_handshake", "u1"), ("n_ccs", "u1"),
+     ("n_alert", "u1"), ("n_appdata", "u1"), ("n_hellos", "u1"), ("flags", "u1")]
+)
+SSL_HELLO_DTYPE = np.dtype(
+    [("name_pos", "<u8"), ("msg", "<u4"), ("msg_offset", "<u2"), ("name_len", "<u2"), ("version", "<u2"),
+     ("header_version", "<u2"), ("cipher", "<u2"), ("n_ciphers", "<u2"), ("n_ext", "<u2"), ("kind", "u1"),
+     ("layer", "u1"), ("session_id_len", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
+)
+assert SSL_MSG_DTYPE.itemsize == 32 and SSL_HELLO_DTYPE.itemsize == 32
+
+
+class SslSpec(C.Structure):
+    """pcppx_ssl_spec: the room for SSL packets (0 = n) and the hello kinds that get records."""
+    _fields_ = [("max_msgs", C.c_uint32), ("kinds", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class SslMsg(C.Structure):
+    """pcppx_ssl_msg (SSL_MSG_DTYPE is its numpy mirror)."""
+    _fields_ = [("first_hello", C.c_uint64), ("index", C.c_uint32), ("name_bytes", C.c_uint32),
+                ("layer_offset", C.c_uint16), ("payload_len", C.c_uint16), ("src_port", C.c_uint16),
+                ("dst_port", C.c_uint16), ("ssl_port", C.c_uint16), ("n_handshake", C.c_uint8), ("n_ccs", C.c_uint8),
+                ("n_alert", C.c_uint8), ("n_appdata", C.c_uint8), ("n_hellos", C.c_uint8), ("flags", C.c_uint8)]
+
+
+class SslHello(C.Structure):
+    """pcppx_ssl_hello (SSL_HELLO_DTYPE is its numpy mirror)."""
+    _fields_ = [("name_pos", C.c_uint64), ("msg", C.c_uint32), ("msg_offset", C.c_uint16), ("name_len", C.c_uint16),
+                ("version", C.c_uint16), ("header_version", C.c_uint16), ("cipher", C.c_uint16),
+                ("n_ciphers", C.c_uint16), ("n_ext", C.c_uint16), ("kind", C.c_uint8), ("layer", C.c_uint8),
+                ("session_id_len", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class SslOut(C.Structure):
+    """pcppx_ssl_out: the messages, the hello records, the host names back to back, the disposition and the totals."""
+    _fields_ = [("msgs", C.c_void_p), ("hellos", C.c_void_p), ("names", C.c_void_p), ("names_cap", C.c_uint64),
+                ("disposition", C.c_void_p), ("max_msgs", C.c_uint32), ("max_hellos", C.c_uint32),
+                ("totals", C.c_void_p)]
+
+
+def make_ssl_spec(kinds: int = 3, max_msgs: int = 0) -> SslSpec:
+    return SslSpec(max_msgs, kinds)
+
+
+def ssl_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(SSL_TOTAL_NAMES)}
+
+
+def ssl_reference(batch: Batch, records: Records, max_layers: int, spec: SslSpec, out: SslOut) -> None:
+    """pcppx_ssl_reference: pcppx_ssl_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_ssl_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                            C.byref(out)), "pcppx_ssl_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -838,6 +905,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_http_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(HttpSpec),
                                          C.POINTER(HttpOut)]
     lib.pcppx_http_reference.restype = C.c_int
+    lib.pcppx_ssl_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(SslSpec),
+                                     C.POINTER(SslOut), P]
+    lib.pcppx_ssl_device.restype = C.c_int
+    lib.pcppx_ssl_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(SslSpec),
+                                        C.POINTER(SslOut)]
+    lib.pcppx_ssl_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -869,6 +942,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_tcpstream_device", "pcppx_tcpstream_reference", "pcppx_tlsfp_device", "pcppx_tlsfp_reference",
     "pcppx_dns_device", "pcppx_dns_reference",
     "pcppx_http_device", "pcppx_http_reference",
+    "pcppx_ssl_device", "pcppx_ssl_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

@@ -22,6 +22,7 @@
 #include "pcppx_tlsfp.h"
 #include "pcppx_dns.h"
 #include "pcppx_http.h"
+#include "pcppx_ssl.h"
 
 namespace
 {
@@ -256,6 +257,8 @@ struct pcppx_ctx
 	Scratch dns;
 	// pcppx_http_device: the per-packet plans and the block sums and bases (http_scratch_bytes)
 	Scratch http;
+	// pcppx_ssl_device: the per-packet plans and the block sums and bases (ssl_scratch_bytes)
+	Scratch ssl;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -942,6 +945,8 @@ extern "C"
 		c->dns.release(c->stream);
 		c->http.wait();
 		c->http.release(c->stream);
+		c->ssl.wait();
+		c->ssl.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -953,7 +958,7 @@ extern "C"
 			(void)hipHostFree(c->h_win);
 		}
 		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag,
-		                         &c->tlsfp, &c->dns, &c->http })
+		                         &c->tlsfp, &c->dns, &c->http, &c->ssl })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1930,6 +1935,32 @@ extern "C"
 		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
 		rc = pcppx::launch_http(b, r->layers, max_layers, rec0, stride, s, o, c->http.ptr, st);
 		return rc != PCPPX_OK ? rc : c->http.mark_used(st);
+	}
+}
+
+// ---- ssl: the SSL/TLS records, the hellos and the SNI of the SSL packets of a batch (include/pcppx.h, ssl) ----
+// pcppx_ssl_reference is pcppx_ssl_ref.cpp (plain C++); the argument rules both calls share are pcppx_ssl.h's
+extern "C"
+{
+	int pcppx_ssl_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                     const pcppx_ssl_spec* s, pcppx_ssl_out* o, void* hip_stream)
+	{
+		if (c == nullptr || !pcppx::ssl::valid_args(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_SSL_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous ssl call (possibly queued on another stream) owns the plans until it is done
+		int rc = c->ssl.acquire(st, pcppx::ssl_scratch_bytes(b->n));
+		if (rc != PCPPX_OK)
+			return rc;
+		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+		                                            : reinterpret_cast<const uint8_t*>(r->brief);
+		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+		rc = pcppx::launch_ssl(b, r->layers, max_layers, rec0, stride, s, o, c->ssl.ptr, st);
+		return rc != PCPPX_OK ? rc : c->ssl.mark_used(st);
 	}
 }
 

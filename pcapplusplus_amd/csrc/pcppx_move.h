@@ -1,5 +1,5 @@
 // pcppx_move.h — device primitives shared by the operators that read or move the packets of a device batch
-// (pcppx_select.hip, pcppx_steer.hip, pcppx_bpf.hip, pcppx_defrag.hip, pcppx_frag.hip, pcppx_tlsfp.hip, pcppx_dns.hip, pcppx_http.hip): the descriptor rule, 64-bit
+// (pcppx_select.hip, pcppx_steer.hip, pcppx_bpf.hip, pcppx_defrag.hip, pcppx_frag.hip, pcppx_tlsfp.hip, pcppx_dns.hip, pcppx_http.hip, pcppx_ssl.hip): the descriptor rule, 64-bit
 // wave scans, and the pieces of the aligned 16-B copy idiom. Inline device functions only; pcppx_kernels.hip keeps its
 // own 32-bit helpers.
 #pragma once

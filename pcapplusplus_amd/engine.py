@@ -338,6 +338,26 @@ class Engine:
         abi.check(self.lib.pcppx_http_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_http_device")
 
+    def ssl_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.SslSpec,
+                   msgs, hellos, totals, max_msgs: int, max_hellos: int, names=None, names_cap: int = 0,
+                   disposition=None, stream: int | None = None, data_len: int | None = None, summary=None,
+                   brief=None) -> None:
+        """Queue pcppx_ssl_device over device tensors: one message (abi.SSL_MSG_DTYPE, 32 bytes) per SSL packet and one
+        record (abi.SSL_HELLO_DTYPE, 32 bytes) per ClientHello / ServerHello spec asks for, with the SNI host names.
+        summary (n * 32 bytes) or brief (n * 16 bytes): the parse's records, one of them; layers: FIXED,
+        n * max_layers * 8 bytes. msgs: max_msgs * 32 bytes; hellos: max_hellos * 32 bytes; names (u8, names_cap bytes;
+        None = positions only); disposition (u8[n], optional); totals: 12 x i64 (abi.SSL_*), overwritten. All or
+        nothing: on overflow only the totals are written. Returns without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.SslOut(abi.ptr(msgs), abi.ptr(hellos), opt(names), names_cap, opt(disposition), max_msgs, max_hellos,
+                         abi.ptr(totals))
+        abi.check(self.lib.pcppx_ssl_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                            C.byref(out), C.c_void_p(stream or 0)), "pcppx_ssl_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -1012,6 +1032,46 @@ def http_on_device(eng: Engine, batch: PacketBatch, spec: abi.HttpSpec | None = 
     assert tot["overflow"] == 0
     return (msgs.cpu().numpy().view(abi.HTTP_MSG_DTYPE)[:m], fields.cpu().numpy().view(abi.HTTP_FIELD_DTYPE)[:k],
             text[:nb].cpu().numpy() if want_text else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
+
+
+def ssl_on_device(eng: Engine, batch: PacketBatch, kinds: int = 3, opts: abi.Opts | None = None,
+                  want_names: bool = True, device: str = "cuda:0"):
+    """Copy a host batch to HBM, parse it there and walk its SSL/TLS records (pcppx_ssl_device) without the records
+    leaving the device in between; copy the result back: (msgs abi.SSL_MSG_DTYPE[m] in source order, hellos
+    abi.SSL_HELLO_DTYPE[k] message by message, names u8 = the SNI host names back to back (empty with want_names =
+    False), hash5 u32[n] = the parse's flow keys (what pcapplusplus_amd.ssl.analyze keys flows by), disposition u8[n] =
+    abi.SSL_* per source packet, totals dict). The buffers are sized by a first call without room, which overflows and
+    writes the totals alone."""
+    import torch
+
+    opts = opts or abi.make_opts()
+    spec = abi.make_ssl_spec(kinds)
+    n, ml = batch.n, opts.max_layers
+    data, offsets, caplens = to_device(batch, device)
+    summary = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=device)
+    layers = torch.zeros(max(n * ml, 1) * 8, dtype=torch.uint8, device=device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, st)
+    totals = torch.empty(abi.SSL_TOTALS, dtype=torch.int64, device=device)
+
+    def call(msgs, max_msgs, hellos, max_hellos, names=None, cap=0, disp=None):
+        eng.ssl_device(data, offsets, caplens, n, batch.linktype, layers, ml, spec, msgs, hellos, totals, max_msgs,
+                       max_hellos, names, cap, disp, st, summary=summary)
+        torch.cuda.synchronize(device)
+        return abi.ssl_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    one = torch.empty(32, dtype=torch.uint8, device=device)
+    need = call(one, 0, one, 0)
+    m, k, nb = need["msgs"], need["hellos"], need["name_bytes"]
+    msgs = torch.empty(max(m, 1) * 32, dtype=torch.uint8, device=device)
+    hellos = torch.empty(max(k, 1) * 32, dtype=torch.uint8, device=device)
+    names = torch.empty(max(nb, 1), dtype=torch.uint8, device=device) if want_names else None
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(msgs, m, hellos, k, names, nb, disp)
+    assert tot["overflow"] == 0
+    hash5 = summary.cpu().numpy().view(abi.SUMMARY_DTYPE)[:n]["hash5"].copy()
+    return (msgs.cpu().numpy().view(abi.SSL_MSG_DTYPE)[:m], hellos.cpu().numpy().view(abi.SSL_HELLO_DTYPE)[:k],
+            names[:nb].cpu().numpy() if want_names else np.zeros(0, np.uint8), hash5, disp[:n].cpu().numpy(), tot)
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
