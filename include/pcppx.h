@@ -1737,6 +1737,213 @@ PCPPX_API int pcppx_ssl_device(pcppx_ctx* ctx, const pcppx_batch* batch, const p
 PCPPX_API int pcppx_ssl_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                   const pcppx_ssl_spec* spec, pcppx_ssl_out* out);
 
+/* ---- sip: the SIP messages, their header fields and their SDP bodies of a device batch ----
+ * What SipRequestLayer / SipResponseLayer and the SdpLayer behind them give a VoIP monitor (Packet++/src/SipLayer.cpp,
+ * SdpLayer.cpp, TextBasedProtocol.cpp), for packets that sit in HBM: per SIP packet one message record (the method or
+ * the status code, the URI or the status text, header length, field count, content length), per header field the
+ * caller asked for one record (Call-ID, From, To, CSeq ...), the bytes it asked for back to back, and per SDP body one
+ * record (the owner address and the audio / video RTP ports). Added within ABI 7: new symbols only.
+ *
+ * The parse records hold no SIP layer: it runs the reference's four-byte SIP test (SipLayer::detectSipMessageType) and
+ * the port test, flags the packet PCPPX_F_NEEDS_HOST_L7 and stops the chain at the L4 layer. So this operator restates
+ * the reference's dispatch itself, from the recorded carrier (TCP / UDP) entry and the payload bytes.
+ *
+ * Inputs: as http. A device batch and its FIXED records (max_layers >= 1, the same value as the parse used; the summary
+ * or, when it is NULL, the brief supplies flags and n_layers; PACKED and DENSE records are refused).
+ *
+ * Per packet i the first rule that applies decides. Positions count from the SIP layer's first byte (the carrier's
+ * first payload byte); d[x] is the byte at x, L the payload length:
+ *   1 BAD_DESC. offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (pcppx_move.h's out_of_bounds, as
+ *     everywhere else): the packet is never read.
+ *   2 Incomplete chain -> HOST: flags has PCPPX_F_NEEDS_HOST_PROTO, OVERSIZE, BAD_DESC or DEPTH_OVERFLOW, or n_layers >
+ *     max_layers, or NEEDS_HOST_L7 is set without L7_KNOWN (the VXLAN / GTP tunnels whose inner packet only the host
+ *     parses).
+ *   3 No candidate -> NONE: NEEDS_HOST_L7 is clear (the device built the whole chain: the reference builds a Payload
+ *     there), or one of L7_HTTP / L7_SSL / L7_DNS is set (the device named another first L7 layer).
+ *   4 The carrier: the last entry k < n_layers whose proto is 4 (pcpp::TCP) or 5 (pcpp::UDP). It must be the last
+ *     entry, or be followed by one PacketTrailer (30) entry that is the last; it must lie inside the packet (8 <=
+ *     hdr_len < data_len and offset + data_len <= caplen). Otherwise NONE. The payload is [offset + hdr_len, offset +
+ *     data_len), L = data_len - hdr_len; the ports are the header's bytes 0..3 (big-endian source, destination).
+ *   5 UDP, in UdpLayer::parseNextLayer's order (UdpLayer.cpp:103-183): the DHCP port pair (68->67, 67->68, 67->67) ->
+ *     NONE; destination 4789 -> NONE; either port 5060 / 5061 -> the port path, rule 7. Otherwise the heuristic path:
+ *     L < 4, or d[0..3] is none of the 15 keys "INVI" "ACK " "BYE " "CANC" "REGI" "PRAC" "OPTI" "SUBS" "NOTI" "PUBL"
+ *     "INFO" "REFE" "MESS" "UPDA" "SIP/" (SipLayer.cpp:127-160) -> NONE. With a key, a port that gates a dissector of
+ *     UdpLayer.cpp:122-165 -> HOST (whether that dissector takes the payload is the host's answer): either port 1812,
+ *     1813, 3799 (RADIUS), 2152, 2123 (GTP), 546, 547 (DHCPv6), 123 (NTP), 13400, 3496 (DoIP), 30490 (SOME/IP's default
+ *     port), 51820 (WireGuard), or destination 0, 7, 9 (WoL). Otherwise rule 8.
+ *   6 TCP (TcpLayer.cpp:372-402; the HTTP and SSL branches ahead are excluded by rule 3): a port 5060 / 5061 on either
+ *     side -> the port path, rule 7. Otherwise NONE: TCP has no heuristic.
+ *   7 The port path (the six-argument SipLayer::parseSipLayer, SipLayer.cpp:162-184; TcpLayer.cpp:389-401). The
+ *     method (SipRequestFirstLine::parseMethod :291-315) is the text before the first space, looked up among INVITE
+ *     ACK BYE CANCEL REGISTER PRACK OPTIONS SUBSCRIBE NOTIFY PUBLISH INFO REFER MESSAGE UPDATE (0..13); it needs L >= 4
+ *     and the space at 1..L-1. A known method -> a request. Otherwise the status code (parseStatusCode :1039-1054): L >=
+ *     12, d[11] == ' ' and code = ((int8)d[8] - 48) * 100 + ((int8)d[9] - 48) * 10 + ((int8)d[10] - 48), the bytes
+ *     sign-extended and the sum taken modulo 2^16 (parseStatusCodePure :695-705), is one of the 77 codes of the switch
+ *     (:707-871). A known code -> a response; on UDP only when parseVersion (:1127-1146) is not empty too: L >= 8,
+ *     d[0..3] == "SIP/" and a ' ' exists in [0, L). Otherwise NONE.
+ *   8 The heuristic path (the four-argument parseSipLayer :186-209), via = 1. A request key: the method must be
+ *     known, and SipRequestFirstLine::parseFirstLine (:317-393) must hold: with s1 the first space, a second space s2
+ *     in (s1, L); s2 - s1 - 1 > 0 (the URI); with e the first '\r' or '\n' in (s2, L), else L, e - s2 - 1 >= 7; and
+ *     d[s2+1..s2+4] == "SIP/". Otherwise NONE. The "SIP/" key (SipResponseFirstLine::parseFirstLine :1148-1196): L <
+ *     12 -> NONE; s the first ' ' in [4, L), none -> NONE; the reference then reads d[s + 4] without a bound: with
+ *     s + 4 >= L its answer is undefined and the packet is HOST; d[s + 4] != ' ' -> NONE; the code of d[s+1..s+3]
+ *     (rule 7's arithmetic) unknown -> NONE; otherwise a response.
+ *     A message whose kind is not in spec->kinds is NONE (HOST verdicts of rules 5 and 8 come first).
+ *   9 A request's first line as the layer stores it (the constructor :213-246, parseVersion :395-433, getUri
+ *     :479-489). u = len(method) + 1; v is the first " SIP/" in [u, L). With no v, or v + 7 > L, the version is
+ *     unknown (m_VersionOffset = -1): there is no URI, and the '\n' that ends the line is searched from one byte
+ *     before the layer -- the carrier header's last byte -- over L + 1 bytes. That is kept bit for bit: when that
+ *     byte is 0x0A, first_line_len is 0 (and the line is complete); otherwise first_line_len is one past the first
+ *     '\n' in [0, L), else L and not complete. The byte is in bounds by rule 4. With v, VERSION_KNOWN is set, the URI
+ *     is [u, v), and with e the first '\n' in [v + 1, L) first_line_len = e + 1 (complete), else L (not complete).
+ *  10 A response's first line (the constructor :1056-1079, getStatusCodeString :952-968). VERSION_KNOWN is rule 7's
+ *     parseVersion. status_code is getStatusCodeAsInt() of rule 7's code when the version is known and the code is
+ *     known, else 0: the code itself, but 425 for 423, 423 for 424 and 424 for 425, as the reference's
+ *     StatusCodeEnumToInt (:687-692) lists those three in another order than its enum. That is kept.
+ *     first_line_len is one past the first '\n' in [0, L) (complete), else L. With a status code the status text
+ *     starts at 12 and ends at x = first_line_len - 2, or at x + 1 when d[x] != '\r'; a text that would end at or
+ *     before 12 is empty (the reference's getStatusCodeString has no defined answer there).
+ *  11 The fields: http's rules 6-8 exactly (the same parseFields, ':' as separator, spaces skipped), from
+ *     first_line_len.
+ *  12 content_length (SipLayer::getContentLength :57-66): http's rule 9 -- the first non-end field whose lowered name
+ *     is "content-length". The compact name "l" is not recognised.
+ *  13 SDP (SipLayer::parseNextLayer :85-110). HAS_SDP is set when L > header_len, content_length > 0 and the first
+ *     non-end field whose lowered name is "content-type" has a value that contains the 15 bytes "application/sdp"
+ *     (case-sensitive, std::string::find over all the value's bytes, NULs included). The body is [header_len, L); its
+ *     fields are walked from its byte 0 as rule 11 walks, with '=' as the separator and no space skipped
+ *     (SdpLayer.cpp:21-26, SdpLayer.h:156-163). Tokens are the value's runs of bytes other than " \t\n\v\f\r".
+ *     Owner (getOwnerIPv4Address :74-95): the first field named "o" (one byte, 'O' too); it needs a value of >= 6
+ *     tokens with token 3 == "IN" and token 4 == "IP4"; token 5, cut at its first NUL, is parsed as inet_pton(AF_INET)
+ *     parses (IpAddress.cpp:63-69): four decimal numbers <= 255 of 1..3 digits, no leading zero before another digit,
+ *     single dots between, nothing else. HAS_OWNER is set when the address parses and is not 0.0.0.0. Media
+ *     (getMediaPort :97-114): the first field named "m" whose value has >= 2 tokens and token 0 == "audio" (resp.
+ *     "video"): HAS_AUDIO (HAS_VIDEO), and the port is atoi of token 1 cut at its first NUL -- one optional sign, then
+ *     digits, saturating at the 64-bit long's limits as strtol does -- cut to 16 bits.
+ *  14 Source bytes are read only inside the carrier's payload of in-bounds packets, plus the carrier header's four
+ *     port bytes and its last byte (rule 9). */
+typedef pcppx_http_spec pcppx_sip_spec; /* 272 bytes, the same fields: max_msgs (0 = n); kinds (bit 0 requests, bit 1
+                                           responses); fields (NONE / WANTED / ALL); text (bit 0 the URI / the status
+                                           text, bit 1 the values of wanted fields); n_names <= 8 lower-case names of
+                                           1..32 bytes, e.g. "call-id", "from", "to", "cseq" */
+typedef pcppx_http_field pcppx_sip_field; /* 24 bytes: http's field record, offsets from the SIP layer's first byte */
+
+#define PCPPX_SIP_REQUEST 0 /* pcppx_sip_msg.kind */
+#define PCPPX_SIP_RESPONSE 1
+#define PCPPX_SIP_METHOD_UNKNOWN 14 /* pcppx_sip_msg.method: SipMethod 0..13 (INVITE ACK BYE CANCEL REGISTER PRACK
+                                       OPTIONS SUBSCRIBE NOTIFY PUBLISH INFO REFER MESSAGE UPDATE); a response: this */
+#define PCPPX_SIP_VIA_PORT 0 /* pcppx_sip_msg.via: rule 7 */
+#define PCPPX_SIP_VIA_HEURISTIC 1 /* rule 8 */
+
+/* pcppx_sip_msg.flags */
+#define PCPPX_SIP_FIRST_LINE_COMPLETE 1  /* the first line's isComplete() */
+#define PCPPX_SIP_HEADER_COMPLETE 2      /* isHeaderComplete() */
+#define PCPPX_SIP_HAS_CONTENT_LENGTH 4   /* getFieldByName("content-length") finds a field */
+#define PCPPX_SIP_CONTENT_LENGTH_RANGE 8 /* its number does not fit an int: content_length is 0 */
+#define PCPPX_SIP_VERSION_KNOWN 16       /* the first line's getVersion() is not empty */
+#define PCPPX_SIP_HAS_SDP 32             /* an SdpLayer follows: one pcppx_sip_sdp record */
+#define PCPPX_SIP_CARRIER_TCP 64         /* the carrier is TCP */
+
+typedef struct pcppx_sip_msg { /* 48 bytes per SIP packet, in source order */
+	uint64_t first_field;    /* record number in out->fields of its first field record */
+	uint64_t text_pos;       /* its first byte in out->text */
+	uint32_t index;          /* source packet number (strictly ascending) */
+	int32_t content_length;  /* getContentLength(), rule 12 */
+	uint16_t layer_offset;   /* the SIP layer's first byte, from the packet's first byte */
+	uint16_t layer_len;      /* L */
+	uint16_t header_len;     /* getHeaderLen() */
+	uint16_t first_line_len; /* the first line's getSize() */
+	uint16_t n_fields;       /* getFieldCount(), whatever spec->fields says */
+	uint16_t n_rec;          /* the field records emitted for it */
+	uint16_t a_offset;       /* request: the URI; response: the status text; from the layer's first byte */
+	uint16_t a_len;          /* 0 with a_offset 0 when there is none */
+	uint16_t status_code;    /* response: getStatusCodeAsInt(), 0 = unknown; request: 0 */
+	uint16_t text_len;       /* the bytes it put into out->text */
+	uint8_t kind;            /* PCPPX_SIP_REQUEST / PCPPX_SIP_RESPONSE */
+	uint8_t method;          /* request: SipMethod 0..13; response: 14 */
+	uint8_t via;             /* PCPPX_SIP_VIA_PORT / PCPPX_SIP_VIA_HEURISTIC */
+	uint8_t flags;           /* PCPPX_SIP_* above */
+} pcppx_sip_msg;
+
+/* pcppx_sip_sdp.flags */
+#define PCPPX_SIP_SDP_HAS_OWNER 1 /* getOwnerIPv4Address() != 0.0.0.0 */
+#define PCPPX_SIP_SDP_HAS_AUDIO 2 /* an "m" field with >= 2 tokens and "audio" first exists */
+#define PCPPX_SIP_SDP_HAS_VIDEO 4
+
+typedef struct pcppx_sip_sdp { /* 32 bytes per message with HAS_SDP, in message order */
+	uint32_t msg;          /* its message's record number in out->msgs */
+	uint32_t index;        /* source packet number */
+	uint16_t offset;       /* the body's first byte, from the SIP layer's first byte (= header_len) */
+	uint16_t len;          /* L - header_len */
+	uint16_t n_fields;     /* the SdpLayer's getFieldCount() */
+	uint16_t audio_port;   /* getMediaPort("audio"); 0 without HAS_AUDIO */
+	uint16_t video_port;   /* getMediaPort("video"); 0 without HAS_VIDEO */
+	uint8_t flags;         /* PCPPX_SIP_SDP_* */
+	uint8_t reserved0;     /* 0 */
+	uint8_t owner_ipv4[4]; /* getOwnerIPv4Address(), network order; zeros without HAS_OWNER */
+	uint8_t reserved[8];   /* 0 */
+} pcppx_sip_sdp;
+
+/* pcppx_sip_out.disposition values */
+#define PCPPX_SIP_NONE 0     /* the reference builds no SIP layer of a kind in spec->kinds here */
+#define PCPPX_SIP_MSG 1      /* a message record */
+#define PCPPX_SIP_HOST 2     /* only the host can tell (rules 2, 5 and 8) */
+#define PCPPX_SIP_BAD_DESC 3 /* the descriptor is out of bounds: never read */
+
+/* pcppx_sip_out.totals words */
+#define PCPPX_SIP_MSGS 0
+#define PCPPX_SIP_REQUESTS 1
+#define PCPPX_SIP_RESPONSES 2
+#define PCPPX_SIP_FIELDS 3        /* the field records emitted */
+#define PCPPX_SIP_TEXT_BYTES 4
+#define PCPPX_SIP_HOST_N 5
+#define PCPPX_SIP_BAD_DESC_N 6
+#define PCPPX_SIP_HEADER_BYTES 7  /* the sum of header_len */
+#define PCPPX_SIP_FIELDS_LINKED 8 /* the sum of n_fields */
+#define PCPPX_SIP_SDPS 9          /* the SDP records emitted */
+#define PCPPX_SIP_BY_HEURISTIC 10 /* messages with via == PCPPX_SIP_VIA_HEURISTIC */
+#define PCPPX_SIP_OVERFLOW 11
+#define PCPPX_SIP_TOTALS 12
+
+typedef struct pcppx_sip_out { /* device pointers; host pointers for pcppx_sip_reference */
+	pcppx_sip_msg* msgs;     /* max_msgs entries, in source order */
+	pcppx_sip_field* fields; /* max_fields entries: message by message, each in walk order */
+	pcppx_sip_sdp* sdps;     /* max_sdps entries, in message order */
+	uint8_t* text;           /* the messages' text back to back in record order, no terminator; NULL = no text */
+	uint64_t text_cap;
+	uint8_t* disposition;    /* optional (NULL): n entries, PCPPX_SIP_* per source packet */
+	uint32_t max_msgs;
+	uint32_t max_fields;
+	uint32_t max_sdps;
+	uint32_t reserved;       /* 0 */
+	uint64_t* totals;        /* PCPPX_SIP_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_sip_out;
+
+/* Capacity is all or nothing, as in http: OVERFLOW = 1 iff MSGS > out->max_msgs, or FIELDS > max_fields, or SDPS >
+ * max_sdps, or text != NULL and TEXT_BYTES > text_cap, or MSGS > spec->max_msgs (0 = n). Then only the totals are
+ * written (no record, no byte of text, no disposition); they always hold the full would-be values. With text == NULL
+ * positions and lengths are still filled and the byte capacity is not applied. Sizing: a call with max_msgs =
+ * max_fields = max_sdps = 0 overflows (when there is a message) and gives MSGS, FIELDS, SDPS and TEXT_BYTES. The cost
+ * of a packet is linear in its payload's L bytes.
+ * Nothing is written outside the first MSGS messages, the first FIELDS records, the first SDPS records, [0,
+ * TEXT_BYTES) of text and the n dispositions. The output is a pure function of the inputs, bit-identical from run to
+ * run: positions come from counts and scans, and there are no atomics. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: http's list (a null ctx, batch, records, spec, out, totals, msgs or fields;
+ * with n > 0 a null records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers
+ * 0 or above PCPPX_MAX_LAYERS; kinds 0 or above 3; fields above 2; text above 3; n_names above 8; a name_len of 0 or
+ * above 32 for k < n_names, or not 0 beyond; a byte 'A'..'Z' in a name; two equal names), plus a null sdps and a
+ * non-zero out->reserved. The work is queued on hip_stream and the call returns without waiting; calls on one context
+ * are ordered through its sip scratch (a buffer and an event of their own, as http's). Scratch: with g = ceil(n / 1024)
+ * blocks, 76 g + 16 n bytes (per block eleven 32-bit sums -- its messages, field records, text bytes, SDP records,
+ * requests, responses, HOST and BAD_DESC packets, header bytes, linked fields and heuristic-path messages -- and the
+ * 64-bit exclusive prefixes of the first four; per packet a 16-byte plan: the layer's offset and length, the kind, the
+ * path, the records and text bytes of the message, its header length and linked fields, whether it has an SDP body,
+ * and the disposition); PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_sip_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                               uint8_t max_layers, const pcppx_sip_spec* spec, pcppx_sip_out* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_sip_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                  const pcppx_sip_spec* spec, pcppx_sip_out* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

@@ -651,6 +651,85 @@ def ssl_reference(batch: Batch, records: Records, max_layers: int, spec: SslSpec
                                             C.byref(out)), "pcppx_ssl_reference")
 
 
+# pcppx_sip_*: the SIP messages, their header fields and their SDP bodies of a batch (include/pcppx.h, sip)
+SIP_NONE, SIP_MSG, SIP_HOST, SIP_BAD_DESC = range(4)  # disposition
+SIP_REQUEST, SIP_RESPONSE = 0, 1                      # msg.kind
+SIP_VIA_PORT, SIP_VIA_HEURISTIC = 0, 1                # msg.via
+SIP_METHODS = ("INVITE", "ACK", "BYE", "CANCEL", "REGISTER", "PRACK", "OPTIONS", "SUBSCRIBE", "NOTIFY", "PUBLISH",
+               "INFO", "REFER", "MESSAGE", "UPDATE")  # msg.method 0..13
+SIP_METHOD_UNKNOWN = 14
+(SIP_FIRST_LINE_COMPLETE, SIP_HEADER_COMPLETE, SIP_HAS_CONTENT_LENGTH, SIP_CONTENT_LENGTH_RANGE, SIP_VERSION_KNOWN,
+ SIP_HAS_SDP, SIP_CARRIER_TCP) = 1, 2, 4, 8, 16, 32, 64  # msg.flags
+SIP_SDP_HAS_OWNER, SIP_SDP_HAS_AUDIO, SIP_SDP_HAS_VIDEO = 1, 2, 4  # sdp.flags
+(SIP_MSGS, SIP_REQUESTS, SIP_RESPONSES, SIP_FIELDS, SIP_TEXT_BYTES, SIP_HOST_N, SIP_BAD_DESC_N, SIP_HEADER_BYTES,
+ SIP_FIELDS_LINKED, SIP_SDPS, SIP_BY_HEURISTIC, SIP_OVERFLOW) = range(12)  # pcppx_sip_out.totals
+SIP_TOTALS = 12
+SIP_TOTAL_NAMES = ("msgs", "requests", "responses", "fields", "text_bytes", "host_n", "bad_desc", "header_bytes",
+                   "fields_linked", "sdps", "by_heuristic", "overflow")
+SIP_MSG_DTYPE = np.dtype(
+    [("first_field", "<u8"), ("text_pos", "<u8"), ("index", "<u4"), ("content_length", "<i4"), ("layer_offset", "<u2"),
+     ("layer_len", "<u2"), ("header_len", "<u2"), ("first_line_len", "<u2"), ("n_fields", "<u2"), ("n_rec", "<u2"),
+     ("a_offset", "<u2"), ("a_len", "<u2"), ("status_code", "<u2"), ("text_len", "<u2"), ("kind", "u1"),
+     ("method", "u1"), ("via", "u1"), ("flags", "u1")]
+)
+SIP_FIELD_DTYPE = HTTP_FIELD_DTYPE  # pcppx_sip_field is pcppx_http_field
+SIP_SDP_DTYPE = np.dtype(
+    [("msg", "<u4"), ("index", "<u4"), ("offset", "<u2"), ("len", "<u2"), ("n_fields", "<u2"), ("audio_port", "<u2"),
+     ("video_port", "<u2"), ("flags", "u1"), ("reserved0", "u1"), ("owner_ipv4", "u1", (4,)), ("reserved", "u1", (8,))]
+)
+assert SIP_MSG_DTYPE.itemsize == 48 and SIP_SDP_DTYPE.itemsize == 32
+
+SipSpec = HttpSpec    # pcppx_sip_spec is pcppx_http_spec
+SipField = HttpField  # pcppx_sip_field is pcppx_http_field
+
+
+class SipMsg(C.Structure):
+    """pcppx_sip_msg (SIP_MSG_DTYPE is its numpy mirror)."""
+    _fields_ = [("first_field", C.c_uint64), ("text_pos", C.c_uint64), ("index", C.c_uint32),
+                ("content_length", C.c_int32), ("layer_offset", C.c_uint16), ("layer_len", C.c_uint16),
+                ("header_len", C.c_uint16), ("first_line_len", C.c_uint16), ("n_fields", C.c_uint16),
+                ("n_rec", C.c_uint16), ("a_offset", C.c_uint16), ("a_len", C.c_uint16), ("status_code", C.c_uint16),
+                ("text_len", C.c_uint16), ("kind", C.c_uint8), ("method", C.c_uint8), ("via", C.c_uint8),
+                ("flags", C.c_uint8)]
+
+
+class SipSdp(C.Structure):
+    """pcppx_sip_sdp (SIP_SDP_DTYPE is its numpy mirror)."""
+    _fields_ = [("msg", C.c_uint32), ("index", C.c_uint32), ("offset", C.c_uint16), ("len", C.c_uint16),
+                ("n_fields", C.c_uint16), ("audio_port", C.c_uint16), ("video_port", C.c_uint16),
+                ("flags", C.c_uint8), ("reserved0", C.c_uint8), ("owner_ipv4", C.c_uint8 * 4),
+                ("reserved", C.c_uint8 * 8)]
+
+
+class SipOut(C.Structure):
+    """pcppx_sip_out: the messages, the field records, the SDP records, the text back to back, the disposition and the
+    totals."""
+    _fields_ = [("msgs", C.c_void_p), ("fields", C.c_void_p), ("sdps", C.c_void_p), ("text", C.c_void_p),
+                ("text_cap", C.c_uint64), ("disposition", C.c_void_p), ("max_msgs", C.c_uint32),
+                ("max_fields", C.c_uint32), ("max_sdps", C.c_uint32), ("reserved", C.c_uint32),
+                ("totals", C.c_void_p)]
+
+
+SIP_CALL_NAMES = ("call-id", "from", "to", "cseq")  # what a VoIP monitor keys a dialog by
+
+
+def make_sip_spec(names=SIP_CALL_NAMES, fields: int = HTTP_FIELDS_WANTED, text: int = 3, kinds: int = 3,
+                  max_msgs: int = 0) -> HttpSpec:
+    """names: up to 8 field names of 1..32 bytes (str or bytes), lower case; the call refuses anything else."""
+    return make_http_spec(names, fields, text, kinds, max_msgs)
+
+
+def sip_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(SIP_TOTAL_NAMES)}
+
+
+def sip_reference(batch: Batch, records: Records, max_layers: int, spec: HttpSpec, out: SipOut) -> None:
+    """pcppx_sip_reference: pcppx_sip_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_sip_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                            C.byref(out)), "pcppx_sip_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -911,6 +990,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_ssl_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(SslSpec),
                                         C.POINTER(SslOut)]
     lib.pcppx_ssl_reference.restype = C.c_int
+    lib.pcppx_sip_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(HttpSpec),
+                                     C.POINTER(SipOut), P]
+    lib.pcppx_sip_device.restype = C.c_int
+    lib.pcppx_sip_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(HttpSpec),
+                                        C.POINTER(SipOut)]
+    lib.pcppx_sip_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -943,6 +1028,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_dns_device", "pcppx_dns_reference",
     "pcppx_http_device", "pcppx_http_reference",
     "pcppx_ssl_device", "pcppx_ssl_reference",
+    "pcppx_sip_device", "pcppx_sip_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

@@ -22,6 +22,7 @@
 #include "pcppx_tlsfp.h"
 #include "pcppx_dns.h"
 #include "pcppx_http.h"
+#include "pcppx_sip.h"
 #include "pcppx_ssl.h"
 
 namespace
@@ -259,6 +260,8 @@ struct pcppx_ctx
 	Scratch http;
 	// pcppx_ssl_device: the per-packet plans and the block sums and bases (ssl_scratch_bytes)
 	Scratch ssl;
+	// pcppx_sip_device: the per-packet plans and the block sums and bases (sip_scratch_bytes)
+	Scratch sip;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -947,6 +950,8 @@ extern "C"
 		c->http.release(c->stream);
 		c->ssl.wait();
 		c->ssl.release(c->stream);
+		c->sip.wait();
+		c->sip.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -958,7 +963,7 @@ extern "C"
 			(void)hipHostFree(c->h_win);
 		}
 		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag,
-		                         &c->tlsfp, &c->dns, &c->http, &c->ssl })
+		                         &c->tlsfp, &c->dns, &c->http, &c->ssl, &c->sip })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1961,6 +1966,32 @@ extern "C"
 		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
 		rc = pcppx::launch_ssl(b, r->layers, max_layers, rec0, stride, s, o, c->ssl.ptr, st);
 		return rc != PCPPX_OK ? rc : c->ssl.mark_used(st);
+	}
+}
+
+// ---- sip: the SIP messages, their header fields and their SDP bodies of a batch (include/pcppx.h, sip) ----
+// pcppx_sip_reference is pcppx_sip_ref.cpp (plain C++); the argument rules both calls share are pcppx_sip.h's
+extern "C"
+{
+	int pcppx_sip_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                     const pcppx_sip_spec* s, pcppx_sip_out* o, void* hip_stream)
+	{
+		if (c == nullptr || !pcppx::sip::valid_args(b, r, max_layers, s, o))
+			return PCPPX_E_INVAL;
+		if (!ok(hipSetDevice(c->device)))
+			return PCPPX_E_HIP;
+		hipStream_t st = static_cast<hipStream_t>(hip_stream);
+		if (b->n == 0)
+			return ok(hipMemsetAsync(o->totals, 0, PCPPX_SIP_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+		// the context's previous sip call (possibly queued on another stream) owns the plans until it is done
+		int rc = c->sip.acquire(st, pcppx::sip_scratch_bytes(b->n));
+		if (rc != PCPPX_OK)
+			return rc;
+		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+		                                            : reinterpret_cast<const uint8_t*>(r->brief);
+		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+		rc = pcppx::launch_sip(b, r->layers, max_layers, rec0, stride, s, o, c->sip.ptr, st);
+		return rc != PCPPX_OK ? rc : c->sip.mark_used(st);
 	}
 }
 

@@ -128,6 +128,14 @@ uint32_t ssl_blocks(uint32_t n);
 uint64_t ssl_scratch_bytes(uint32_t n);
 int launch_ssl(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
                const pcppx_ssl_spec* spec, const pcppx_ssl_out* out, void* scratch, hipStream_t stream);
+// pcppx_sip_device (pcppx_sip.hip): three launches on `stream` (plan, bases, emit). scratch: sip_scratch_bytes(n)
+// bytes (include/pcppx.h gives the formula); one block takes kSipBlockPk source packets and writes their records; rec0:
+// packet 0's summary or brief, rec_stride bytes apart. Arguments are checked by the caller; n > 0.
+constexpr uint32_t kSipBlockPk = 1024;
+uint32_t sip_blocks(uint32_t n);
+uint64_t sip_scratch_bytes(uint32_t n);
+int launch_sip(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
+               const pcppx_sip_spec* spec, const pcppx_sip_out* out, void* scratch, hipStream_t stream);
 // pcppx_bpf_device (pcppx_bpf.hip): one launch on `stream` (the caller has cleared out->totals on it). insns: the
 // validated programs back to back in device memory; program p is insns[start[p] .. start[p + 1]); uses_mem: bit p set
 // when program p loads from M[] (only then are its slots cleared). Arguments are checked by the caller; n > 0.

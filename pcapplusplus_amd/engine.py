@@ -358,6 +358,27 @@ class Engine:
         abi.check(self.lib.pcppx_ssl_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_ssl_device")
 
+    def sip_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.SipSpec,
+                   msgs, fields, sdps, totals, max_msgs: int, max_fields: int, max_sdps: int, text=None,
+                   text_cap: int = 0, disposition=None, stream: int | None = None, data_len: int | None = None,
+                   summary=None, brief=None) -> None:
+        """Queue pcppx_sip_device over device tensors: one message (abi.SIP_MSG_DTYPE, 48 bytes) per SIP packet, one
+        record (abi.SIP_FIELD_DTYPE, 24 bytes) per header field spec asks for with the bytes spec asks for, and one
+        record (abi.SIP_SDP_DTYPE, 32 bytes) per SDP body. summary (n * 32 bytes) or brief (n * 16 bytes): the parse's
+        records, one of them; layers: FIXED, n * max_layers * 8 bytes. msgs: max_msgs * 48 bytes; fields: max_fields *
+        24 bytes; sdps: max_sdps * 32 bytes; text (u8, text_cap bytes; None = no text); disposition (u8[n], optional);
+        totals: 12 x i64 (abi.SIP_*), overwritten. All or nothing: on overflow only the totals are written. Returns
+        without waiting."""
+        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
+        rec = abi.Records(opt(summary), abi.ptr(layers))
+        rec.brief = opt(brief)
+        out = abi.SipOut(abi.ptr(msgs), abi.ptr(fields), abi.ptr(sdps), opt(text), text_cap, opt(disposition),
+                         max_msgs, max_fields, max_sdps, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_sip_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                            C.byref(out), C.c_void_p(stream or 0)), "pcppx_sip_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -1072,6 +1093,47 @@ def ssl_on_device(eng: Engine, batch: PacketBatch, kinds: int = 3, opts: abi.Opt
     hash5 = summary.cpu().numpy().view(abi.SUMMARY_DTYPE)[:n]["hash5"].copy()
     return (msgs.cpu().numpy().view(abi.SSL_MSG_DTYPE)[:m], hellos.cpu().numpy().view(abi.SSL_HELLO_DTYPE)[:k],
             names[:nb].cpu().numpy() if want_names else np.zeros(0, np.uint8), hash5, disp[:n].cpu().numpy(), tot)
+
+
+def sip_on_device(eng: Engine, batch: PacketBatch, spec: abi.SipSpec | None = None, opts: abi.Opts | None = None,
+                  want_text: bool = True, device: str = "cuda:0"):
+    """Copy a host batch to HBM, parse it there and walk its SIP messages (pcppx_sip_device) without the records
+    leaving the device in between; copy the result back: (msgs abi.SIP_MSG_DTYPE[m] in source order, fields
+    abi.SIP_FIELD_DTYPE[k] message by message, sdps abi.SIP_SDP_DTYPE[s] in message order, text u8 = the bytes spec
+    asks for back to back (empty with want_text = False), disposition u8[n] = abi.SIP_* per source packet, totals
+    dict). spec None: Call-ID, From, To and CSeq with their values and the first line's text. The buffers are sized by
+    a first call without room, which overflows (where there is a message) and writes the totals alone."""
+    import torch
+
+    opts = opts or abi.make_opts()
+    spec = spec or abi.make_sip_spec()
+    n, ml = batch.n, opts.max_layers
+    data, offsets, caplens = to_device(batch, device)
+    summary = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=device)
+    layers = torch.zeros(max(n * ml, 1) * 8, dtype=torch.uint8, device=device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, st)
+    totals = torch.empty(abi.SIP_TOTALS, dtype=torch.int64, device=device)
+
+    def call(msgs, max_msgs, fields, max_fields, sdps, max_sdps, text=None, cap=0, disp=None):
+        eng.sip_device(data, offsets, caplens, n, batch.linktype, layers, ml, spec, msgs, fields, sdps, totals,
+                       max_msgs, max_fields, max_sdps, text, cap, disp, st, summary=summary)
+        torch.cuda.synchronize(device)
+        return abi.sip_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    one = torch.empty(48, dtype=torch.uint8, device=device)
+    need = call(one, 0, one, 0, one, 0)
+    m, k, ns, nb = need["msgs"], need["fields"], need["sdps"], need["text_bytes"]
+    msgs = torch.empty(max(m, 1) * 48, dtype=torch.uint8, device=device)
+    fields = torch.empty(max(k, 1) * 24, dtype=torch.uint8, device=device)
+    sdps = torch.empty(max(ns, 1) * 32, dtype=torch.uint8, device=device)
+    text = torch.empty(max(nb, 1), dtype=torch.uint8, device=device) if want_text else None
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(msgs, m, fields, k, sdps, ns, text, nb, disp)
+    assert tot["overflow"] == 0
+    return (msgs.cpu().numpy().view(abi.SIP_MSG_DTYPE)[:m], fields.cpu().numpy().view(abi.SIP_FIELD_DTYPE)[:k],
+            sdps.cpu().numpy().view(abi.SIP_SDP_DTYPE)[:ns],
+            text[:nb].cpu().numpy() if want_text else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
