@@ -252,16 +252,9 @@ struct pcppx_ctx
 	Scratch tcpstream;
 	// pcppx_frag_device: the block sums and bases and the per-packet plans (frag_scratch_bytes)
 	Scratch frag;
-	// pcppx_tlsfp_device: the per-packet plans and the block sums and bases (tlsfp_scratch_bytes)
-	Scratch tlsfp;
-	// pcppx_dns_device: the per-packet plans and the block sums and bases (dns_scratch_bytes)
-	Scratch dns;
-	// pcppx_http_device: the per-packet plans and the block sums and bases (http_scratch_bytes)
-	Scratch http;
-	// pcppx_ssl_device: the per-packet plans and the block sums and bases (ssl_scratch_bytes)
-	Scratch ssl;
-	// pcppx_sip_device: the per-packet plans and the block sums and bases (sip_scratch_bytes)
-	Scratch sip;
+	// pcppx_tlsfp_device, pcppx_dns_device, pcppx_http_device, pcppx_ssl_device, pcppx_sip_device: each one's per-packet
+	// plans and block sums and bases (<op>_scratch_bytes)
+	Scratch tlsfp, dns, http, ssl, sip;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -1865,133 +1858,79 @@ extern "C"
 	}
 }
 
-// ---- tlsfp: JA3 / JA3S fingerprints of the hello packets of a batch (include/pcppx.h, tlsfp) ----
-// pcppx_tlsfp_reference is pcppx_tlsfp_ref.cpp (plain C++); the argument rules both calls share are pcppx_tlsfp.h's
+// ---- the message operators: tlsfp, dns, http, ssl, sip (include/pcppx.h) ----
+// pcppx_<op>_reference is pcppx_<op>_ref.cpp (plain C++); the argument rules both calls share are pcppx_<op>.h's
+namespace
+{
+// What the five device entries do once the arguments have their verdict (valid: with c there). scratch: the context's
+// own for the operator, which its previous call (possibly queued on another stream) owns until it is done.
+template <class Spec, class Out>
+int message_device(pcppx_ctx* c, bool valid, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+                   const Spec* s, const Out* o, uint32_t n_totals, Scratch pcppx_ctx::*scratch,
+                   uint64_t (*scratch_bytes)(uint32_t),
+                   int (*launch)(const pcppx_batch*, const pcppx_layer*, uint32_t, const uint8_t*, uint32_t, const Spec*,
+                                 const Out*, void*, hipStream_t),
+                   void* hip_stream)
+{
+	if (!valid)
+		return PCPPX_E_INVAL;
+	if (!ok(hipSetDevice(c->device)))
+		return PCPPX_E_HIP;
+	hipStream_t st = static_cast<hipStream_t>(hip_stream);
+	if (b->n == 0)
+		return ok(hipMemsetAsync(o->totals, 0, n_totals * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
+	Scratch& sc = c->*scratch;
+	int rc = sc.acquire(st, scratch_bytes(b->n));
+	if (rc != PCPPX_OK)
+		return rc;
+	const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
+	                                            : reinterpret_cast<const uint8_t*>(r->brief);
+	const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
+	rc = launch(b, r->layers, max_layers, rec0, stride, s, o, sc.ptr, st);
+	return rc != PCPPX_OK ? rc : sc.mark_used(st);
+}
+}  // namespace
+
 extern "C"
 {
 	int pcppx_tlsfp_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
 	                       const pcppx_tlsfp_spec* s, pcppx_tlsfps* o, void* hip_stream)
 	{
-		if (c == nullptr || !pcppx::tlsfp::valid_args(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_TLSFP_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous tlsfp call (possibly queued on another stream) owns the plans until it is done
-		int rc = c->tlsfp.acquire(st, pcppx::tlsfp_scratch_bytes(b->n));
-		if (rc != PCPPX_OK)
-			return rc;
-		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
-		                                            : reinterpret_cast<const uint8_t*>(r->brief);
-		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
-		rc = pcppx::launch_tlsfp(b, r->layers, max_layers, rec0, stride, s, o, c->tlsfp.ptr, st);
-		return rc != PCPPX_OK ? rc : c->tlsfp.mark_used(st);
+		return message_device<pcppx_tlsfp_spec, pcppx_tlsfps>(
+		    c, c != nullptr && pcppx::tlsfp::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o,
+		    PCPPX_TLSFP_TOTALS, &pcppx_ctx::tlsfp, pcppx::tlsfp_scratch_bytes, pcppx::launch_tlsfp, hip_stream);
 	}
-}
 
-// ---- dns: DnsLayer's resource records of the DNS packets of a batch (include/pcppx.h, dns) ----
-// pcppx_dns_reference is pcppx_dns_ref.cpp (plain C++); the argument rules both calls share are pcppx_dns.h's
-extern "C"
-{
 	int pcppx_dns_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
 	                     const pcppx_dns_spec* s, pcppx_dns_out* o, void* hip_stream)
 	{
-		if (c == nullptr || !pcppx::dns::valid_args(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_DNS_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous dns call (possibly queued on another stream) owns the plans until it is done
-		int rc = c->dns.acquire(st, pcppx::dns_scratch_bytes(b->n));
-		if (rc != PCPPX_OK)
-			return rc;
-		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
-		                                            : reinterpret_cast<const uint8_t*>(r->brief);
-		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
-		rc = pcppx::launch_dns(b, r->layers, max_layers, rec0, stride, s, o, c->dns.ptr, st);
-		return rc != PCPPX_OK ? rc : c->dns.mark_used(st);
+		return message_device<pcppx_dns_spec, pcppx_dns_out>(
+		    c, c != nullptr && pcppx::dns::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o, PCPPX_DNS_TOTALS,
+		    &pcppx_ctx::dns, pcppx::dns_scratch_bytes, pcppx::launch_dns, hip_stream);
 	}
-}
 
-// ---- http: the first line and the header fields of the HTTP packets of a batch (include/pcppx.h, http) ----
-// pcppx_http_reference is pcppx_http_ref.cpp (plain C++); the argument rules both calls share are pcppx_http.h's
-extern "C"
-{
 	int pcppx_http_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
 	                      const pcppx_http_spec* s, pcppx_http_out* o, void* hip_stream)
 	{
-		if (c == nullptr || !pcppx::http::valid_args(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_HTTP_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous http call (possibly queued on another stream) owns the plans until it is done
-		int rc = c->http.acquire(st, pcppx::http_scratch_bytes(b->n));
-		if (rc != PCPPX_OK)
-			return rc;
-		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
-		                                            : reinterpret_cast<const uint8_t*>(r->brief);
-		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
-		rc = pcppx::launch_http(b, r->layers, max_layers, rec0, stride, s, o, c->http.ptr, st);
-		return rc != PCPPX_OK ? rc : c->http.mark_used(st);
+		return message_device<pcppx_http_spec, pcppx_http_out>(
+		    c, c != nullptr && pcppx::http::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o, PCPPX_HTTP_TOTALS,
+		    &pcppx_ctx::http, pcppx::http_scratch_bytes, pcppx::launch_http, hip_stream);
 	}
-}
 
-// ---- ssl: the SSL/TLS records, the hellos and the SNI of the SSL packets of a batch (include/pcppx.h, ssl) ----
-// pcppx_ssl_reference is pcppx_ssl_ref.cpp (plain C++); the argument rules both calls share are pcppx_ssl.h's
-extern "C"
-{
 	int pcppx_ssl_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
 	                     const pcppx_ssl_spec* s, pcppx_ssl_out* o, void* hip_stream)
 	{
-		if (c == nullptr || !pcppx::ssl::valid_args(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_SSL_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous ssl call (possibly queued on another stream) owns the plans until it is done
-		int rc = c->ssl.acquire(st, pcppx::ssl_scratch_bytes(b->n));
-		if (rc != PCPPX_OK)
-			return rc;
-		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
-		                                            : reinterpret_cast<const uint8_t*>(r->brief);
-		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
-		rc = pcppx::launch_ssl(b, r->layers, max_layers, rec0, stride, s, o, c->ssl.ptr, st);
-		return rc != PCPPX_OK ? rc : c->ssl.mark_used(st);
+		return message_device<pcppx_ssl_spec, pcppx_ssl_out>(
+		    c, c != nullptr && pcppx::ssl::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o, PCPPX_SSL_TOTALS,
+		    &pcppx_ctx::ssl, pcppx::ssl_scratch_bytes, pcppx::launch_ssl, hip_stream);
 	}
-}
 
-// ---- sip: the SIP messages, their header fields and their SDP bodies of a batch (include/pcppx.h, sip) ----
-// pcppx_sip_reference is pcppx_sip_ref.cpp (plain C++); the argument rules both calls share are pcppx_sip.h's
-extern "C"
-{
 	int pcppx_sip_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
 	                     const pcppx_sip_spec* s, pcppx_sip_out* o, void* hip_stream)
 	{
-		if (c == nullptr || !pcppx::sip::valid_args(b, r, max_layers, s, o))
-			return PCPPX_E_INVAL;
-		if (!ok(hipSetDevice(c->device)))
-			return PCPPX_E_HIP;
-		hipStream_t st = static_cast<hipStream_t>(hip_stream);
-		if (b->n == 0)
-			return ok(hipMemsetAsync(o->totals, 0, PCPPX_SIP_TOTALS * sizeof(uint64_t), st)) ? PCPPX_OK : PCPPX_E_HIP;
-		// the context's previous sip call (possibly queued on another stream) owns the plans until it is done
-		int rc = c->sip.acquire(st, pcppx::sip_scratch_bytes(b->n));
-		if (rc != PCPPX_OK)
-			return rc;
-		const uint8_t* rec0 = r->summary != nullptr ? reinterpret_cast<const uint8_t*>(r->summary)
-		                                            : reinterpret_cast<const uint8_t*>(r->brief);
-		const uint32_t stride = r->summary != nullptr ? sizeof(pcppx_summary) : sizeof(pcppx_brief);
-		rc = pcppx::launch_sip(b, r->layers, max_layers, rec0, stride, s, o, c->sip.ptr, st);
-		return rc != PCPPX_OK ? rc : c->sip.mark_used(st);
+		return message_device<pcppx_sip_spec, pcppx_sip_out>(
+		    c, c != nullptr && pcppx::sip::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o, PCPPX_SIP_TOTALS,
+		    &pcppx_ctx::sip, pcppx::sip_scratch_bytes, pcppx::launch_sip, hip_stream);
 	}
 }
 

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "pcppx.h"
+#include "pcppx_args.h"
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -29,10 +30,8 @@ constexpr uint32_t kNoColon = 0xFFFFFFFFu;
 inline bool valid_args(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_http_spec* s,
                        const pcppx_http_out* o)
 {
-	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->msgs == nullptr ||
+	if (!valid_source(b, r, max_layers) || s == nullptr || o == nullptr || o->totals == nullptr || o->msgs == nullptr ||
 	    o->fields == nullptr)
-		return false;
-	if (max_layers == 0 || max_layers > PCPPX_MAX_LAYERS || r->layout != PCPPX_LAYOUT_FIXED)
 		return false;
 	if (s->kinds == 0 || s->kinds > 3 || s->fields > PCPPX_HTTP_FIELDS_ALL || s->text > 3 ||
 	    s->n_names > PCPPX_HTTP_MAX_NAMES)
@@ -49,9 +48,7 @@ inline bool valid_args(const pcppx_batch* b, const pcppx_records* r, uint8_t max
 			if (s->name_len[q] == len && memcmp(s->names[q], s->names[k], len) == 0)
 				return false;
 	}
-	if (b->n != 0 && (r->layers == nullptr || (r->summary == nullptr && r->brief == nullptr)))
-		return false;
-	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+	return true;
 }
 
 // What rules 2-3 find in an in-bounds packet: its disposition, and for MSG the layer's first byte (from the packet's

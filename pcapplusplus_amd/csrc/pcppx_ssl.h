@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "pcppx.h"
+#include "pcppx_args.h"
 #include "pcppx_tlsfp.h"
 
 #define PCPPX_SSL_FN PCPPX_TLSFP_FN
@@ -26,16 +27,10 @@ constexpr uint32_t kCcs = 20, kAlert = 21, kHandshake = 22, kAppData = 23;
 inline bool valid_args(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_ssl_spec* s,
                        const pcppx_ssl_out* o)
 {
-	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->msgs == nullptr ||
+	if (!valid_source(b, r, max_layers) || s == nullptr || o == nullptr || o->totals == nullptr || o->msgs == nullptr ||
 	    o->hellos == nullptr)
 		return false;
-	if (max_layers == 0 || max_layers > PCPPX_MAX_LAYERS || r->layout != PCPPX_LAYOUT_FIXED)
-		return false;
-	if (s->kinds > 3 || s->reserved[0] != 0 || s->reserved[1] != 0 || s->reserved[2] != 0)
-		return false;
-	if (b->n != 0 && (r->layers == nullptr || (r->summary == nullptr && r->brief == nullptr)))
-		return false;
-	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+	return s->kinds <= 3 && s->reserved[0] == 0 && s->reserved[1] == 0 && s->reserved[2] == 0;
 }
 
 // SSLLayer::isSSLPort (SSLLayer.h:488-510)

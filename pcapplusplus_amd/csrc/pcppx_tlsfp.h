@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "pcppx.h"
+#include "pcppx_args.h"
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -27,17 +28,11 @@ constexpr uint32_t kHandshake = 22; // SSL_HANDSHAKE
 inline bool valid_args(const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers, const pcppx_tlsfp_spec* s,
                        const pcppx_tlsfps* o)
 {
-	if (b == nullptr || r == nullptr || s == nullptr || o == nullptr || o->totals == nullptr || o->recs == nullptr)
-		return false;
-	if (max_layers == 0 || max_layers > PCPPX_MAX_LAYERS || r->layout != PCPPX_LAYOUT_FIXED)
+	if (!valid_source(b, r, max_layers) || s == nullptr || o == nullptr || o->totals == nullptr || o->recs == nullptr)
 		return false;
 	if (s->client > 1 || s->server > 1 || (s->client == 0 && s->server == 0))
 		return false;
-	if (s->reserved[0] != 0 || s->reserved[1] != 0 || o->reserved != 0)
-		return false;
-	if (b->n != 0 && (r->layers == nullptr || (r->summary == nullptr && r->brief == nullptr)))
-		return false;
-	return b->n == 0 || (b->offsets != nullptr && b->caplens != nullptr && (b->data != nullptr || b->data_len == 0));
+	return s->reserved[0] == 0 && s->reserved[1] == 0 && o->reserved == 0;
 }
 
 PCPPX_TLSFP_FN uint32_t be16(const uint8_t* p)

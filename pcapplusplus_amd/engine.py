@@ -14,6 +14,21 @@ from . import abi
 from .pcap import PacketBatch
 
 
+def _opt(t):
+    """An optional tensor's address."""
+    return abi.ptr(t) if t is not None else None
+
+
+def _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len):
+    """The (abi.Batch, abi.Records) of a device batch and its parse's records (summary or brief; FIXED layers) as the
+    operators over parsed packets take them; data_len None: all of data."""
+    b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
+                  int(data.numel()) if data_len is None else data_len, n, linktype, 0)
+    rec = abi.Records(_opt(summary), abi.ptr(layers))
+    rec.brief = _opt(brief)
+    return b, rec
+
+
 class Engine:
     def __init__(self, device: int = 0):
         self.lib = abi.load_engine()
@@ -103,10 +118,9 @@ class Engine:
         tuples / flow_keys / proto_stats is given); layers: n*max_layers*8; flow_keys: n int32 (hash5); tuples: n*48
         bytes (5-tuple extracts); proto_stats: 16 x int64, accumulated (collectStats)."""
         b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens), int(data.numel()), n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers) if (layers is not None and opts.max_layers) else None,
-                          opt(flow_keys), opt(tuples), opt(proto_stats))
-        rec.brief = opt(brief)
+        rec = abi.Records(_opt(summary), abi.ptr(layers) if (layers is not None and opts.max_layers) else None,
+                          _opt(flow_keys), _opt(tuples), _opt(proto_stats))
+        rec.brief = _opt(brief)
         abi.check(self.lib.pcppx_parse_batch_device(self.ctx, C.byref(b), C.byref(opts), C.byref(rec),
                                                     C.c_void_p(stream or 0)), "pcppx_parse_batch_device")
 
@@ -163,8 +177,7 @@ class Engine:
         totals: 8 x i64 (abi.SEL_*), overwritten. Returns without waiting."""
         b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
                       int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        sel = abi.Selection(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+        sel = abi.Selection(_opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), _opt(out_index),
                             max_packets, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_select_device(self.ctx, C.byref(b), C.byref(spec), C.byref(sel),
                                                C.c_void_p(stream or 0)), "pcppx_select_device")
@@ -180,8 +193,7 @@ class Engine:
         waiting."""
         b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
                       int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        out = abi.Steering(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
+        out = abi.Steering(_opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), _opt(out_index),
                            abi.ptr(bucket_first), abi.ptr(bucket_pos), max_packets, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_steer_device(self.ctx, C.byref(b), C.byref(spec), C.byref(out),
                                               C.c_void_p(stream or 0)), "pcppx_steer_device")
@@ -214,13 +226,9 @@ class Engine:
     def _defrag(self, call: str, data, offsets, caplens, n, linktype, layers, max_layers, info, spec, out_offsets,
                 out_caplens, totals, max_packets, out_data, data_cap, out_index, out_first, out_frags, disposition,
                 stream, data_len, summary, brief) -> None:
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.Defragged(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
-                            opt(out_first), opt(out_frags), opt(disposition), max_packets, 0, abi.ptr(totals))
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.Defragged(_opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), _opt(out_index),
+                            _opt(out_first), _opt(out_frags), _opt(disposition), max_packets, 0, abi.ptr(totals))
         abi.check(getattr(self.lib, call)(self.ctx, C.byref(b), C.byref(rec), max_layers, abi.ptr(info),
                                           C.byref(spec), C.byref(out), C.c_void_p(stream or 0)), call)
 
@@ -234,13 +242,9 @@ class Engine:
         (u8, data_cap bytes; None = index-only), streams (max_streams * 32 bytes, abi.TCPSTREAM_DTYPE), disposition
         (u8[n]) / seg_stream / seg_pos (i32[n]) optional; totals: 8 x i64 (abi.TCPS_*), overwritten. All or nothing:
         on overflow only the totals are written. Returns without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.TcpStreams(opt(out_data), data_cap, abi.ptr(streams), opt(disposition), opt(seg_stream),
-                             opt(seg_pos), max_streams, 0, abi.ptr(totals))
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.TcpStreams(_opt(out_data), data_cap, abi.ptr(streams), _opt(disposition), _opt(seg_stream),
+                             _opt(seg_pos), max_streams, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_tcpstream_device(self.ctx, C.byref(b), C.byref(rec), max_layers, abi.ptr(info),
                                                   C.byref(spec), C.byref(out), C.c_void_p(stream or 0)),
                   "pcppx_tcpstream_device")
@@ -256,13 +260,9 @@ class Engine:
         (i32) / out_index (i32) / out_frag_no (i16) of max_packets entries, counts (i16[n]), disposition (u8[n]), each
         of the last four optional; totals: 8 x i64 (abi.FRAG_*), overwritten. All or nothing: on overflow only the
         totals are written. Returns without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.Fragmented(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
-                             opt(out_frag_no), opt(counts), opt(disposition), max_packets, 0, abi.ptr(totals))
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.Fragmented(_opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), _opt(out_index),
+                             _opt(out_frag_no), _opt(counts), _opt(disposition), max_packets, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_frag_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_frag_device")
 
@@ -272,13 +272,9 @@ class Engine:
                      stream: int | None = None, data_len: int | None = None, summary=None, brief=None) -> None:
         """Queue pcppx_frag6_device over device tensors: frag_device for the families spec.families names (the IPv6
         packets are split too, with the fragment ids of spec.ids / spec.id_base). The arguments are frag_device's."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.Fragmented(opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), opt(out_index),
-                             opt(out_frag_no), opt(counts), opt(disposition), max_packets, 0, abi.ptr(totals))
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.Fragmented(_opt(out_data), data_cap, abi.ptr(out_offsets), abi.ptr(out_caplens), _opt(out_index),
+                             _opt(out_frag_no), _opt(counts), _opt(disposition), max_packets, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_frag6_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                               C.byref(out), C.c_void_p(stream or 0)), "pcppx_frag6_device")
 
@@ -290,12 +286,8 @@ class Engine:
         bytes): the parse's records, one of them; layers: FIXED, n * max_layers * 8 bytes. recs: max_recs * 40 bytes;
         text (u8, text_cap bytes; None = MD5 only); disposition (u8[n], optional); totals: 8 x i64 (abi.TLSFP_*),
         overwritten. All or nothing: on overflow only the totals are written. Returns without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.Tlsfps(abi.ptr(recs), opt(text), text_cap, opt(disposition), max_recs, 0, abi.ptr(totals))
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.Tlsfps(abi.ptr(recs), _opt(text), text_cap, _opt(disposition), max_recs, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_tlsfp_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                               C.byref(out), C.c_void_p(stream or 0)), "pcppx_tlsfp_device")
 
@@ -308,12 +300,8 @@ class Engine:
         n * max_layers * 8 bytes. msgs: max_msgs * 40 bytes; rrs: max_rrs * 32 bytes; names (u8, names_cap bytes; None =
         no text); disposition (u8[n], optional); totals: 8 x i64 (abi.DNS_*), overwritten. All or nothing: on overflow
         only the totals are written. Returns without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.DnsOut(abi.ptr(msgs), abi.ptr(rrs), opt(names), names_cap, opt(disposition), max_msgs, max_rrs,
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.DnsOut(abi.ptr(msgs), abi.ptr(rrs), _opt(names), names_cap, _opt(disposition), max_msgs, max_rrs,
                          abi.ptr(totals))
         abi.check(self.lib.pcppx_dns_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_dns_device")
@@ -328,12 +316,8 @@ class Engine:
         n * max_layers * 8 bytes. msgs: max_msgs * 48 bytes; fields: max_fields * 24 bytes; text (u8, text_cap bytes;
         None = no text); disposition (u8[n], optional); totals: 12 x i64 (abi.HTTP_*), overwritten. All or nothing: on
         overflow only the totals are written. Returns without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.HttpOut(abi.ptr(msgs), abi.ptr(fields), opt(text), text_cap, opt(disposition), max_msgs, max_fields,
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.HttpOut(abi.ptr(msgs), abi.ptr(fields), _opt(text), text_cap, _opt(disposition), max_msgs, max_fields,
                           abi.ptr(totals))
         abi.check(self.lib.pcppx_http_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                              C.byref(out), C.c_void_p(stream or 0)), "pcppx_http_device")
@@ -348,12 +332,8 @@ class Engine:
         n * max_layers * 8 bytes. msgs: max_msgs * 32 bytes; hellos: max_hellos * 32 bytes; names (u8, names_cap bytes;
         None = positions only); disposition (u8[n], optional); totals: 12 x i64 (abi.SSL_*), overwritten. All or
         nothing: on overflow only the totals are written. Returns without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.SslOut(abi.ptr(msgs), abi.ptr(hellos), opt(names), names_cap, opt(disposition), max_msgs, max_hellos,
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.SslOut(abi.ptr(msgs), abi.ptr(hellos), _opt(names), names_cap, _opt(disposition), max_msgs, max_hellos,
                          abi.ptr(totals))
         abi.check(self.lib.pcppx_ssl_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_ssl_device")
@@ -369,12 +349,8 @@ class Engine:
         24 bytes; sdps: max_sdps * 32 bytes; text (u8, text_cap bytes; None = no text); disposition (u8[n], optional);
         totals: 12 x i64 (abi.SIP_*), overwritten. All or nothing: on overflow only the totals are written. Returns
         without waiting."""
-        b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
-                      int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        rec = abi.Records(opt(summary), abi.ptr(layers))
-        rec.brief = opt(brief)
-        out = abi.SipOut(abi.ptr(msgs), abi.ptr(fields), abi.ptr(sdps), opt(text), text_cap, opt(disposition),
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.SipOut(abi.ptr(msgs), abi.ptr(fields), abi.ptr(sdps), _opt(text), text_cap, _opt(disposition),
                          max_msgs, max_fields, max_sdps, 0, abi.ptr(totals))
         abi.check(self.lib.pcppx_sip_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_sip_device")
@@ -395,9 +371,8 @@ class Engine:
         8 x i64 (abi.BPF_*), overwritten; frame_lens: i32 wire lengths (None: the caplens). Returns without waiting."""
         b = abi.Batch(abi.ptr(data), abi.ptr(offsets), abi.ptr(caplens),
                       int(data.numel()) if data_len is None else data_len, n, linktype, 0)
-        opt = lambda t: abi.ptr(t) if t is not None else None  # noqa: E731
-        out = abi.BpfVerdicts(opt(matched), opt(bucket), opt(ret), abi.ptr(totals))
-        abi.check(self.lib.pcppx_bpf_device(self.ctx, flt.handle, C.byref(b), opt(frame_lens), C.byref(out),
+        out = abi.BpfVerdicts(_opt(matched), _opt(bucket), _opt(ret), abi.ptr(totals))
+        abi.check(self.lib.pcppx_bpf_device(self.ctx, flt.handle, C.byref(b), _opt(frame_lens), C.byref(out),
                                             C.c_void_p(stream or 0)), "pcppx_bpf_device")
 
     def filter_reset(self, capacity: int = 0) -> None:
