@@ -1944,6 +1944,178 @@ PCPPX_API int pcppx_sip_device(pcppx_ctx* ctx, const pcppx_batch* batch, const p
 PCPPX_API int pcppx_sip_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
                                   const pcppx_sip_spec* spec, pcppx_sip_out* out);
 
+/* ---- dhcp: the DHCP and DHCPv6 messages and their options of a device batch ----
+ * What DhcpLayer and DhcpV6Layer give passive asset discovery (Packet++/src/DhcpLayer.cpp, DhcpV6Layer.cpp, the option
+ * walk of Packet++/header/TLVData.h's TLVRecordReader), for packets that sit in HBM: per DHCP / DHCPv6 packet one
+ * message record (the BOOTP header's fields, the message type, the lease time, the server identifier, the option
+ * count), per option the caller asked for one record, and the option values it asked for back to back. Both families
+ * are option lists read by the same reader with two record shapes, so one operator covers both. Added within ABI 7:
+ * new symbols only.
+ *
+ * The parse records hold no DHCP layer: it flags these packets PCPPX_F_NEEDS_HOST_L7 | PCPPX_F_L7_KNOWN and stops the
+ * chain at the UDP layer. So this operator restates UdpLayer::parseNextLayer's dispatch (UdpLayer.cpp:103-141) itself,
+ * from the recorded UDP entry and the ports.
+ *
+ * Inputs: as sip. A device batch and its FIXED records (max_layers >= 1, the same value as the parse used; the summary
+ * or, when it is NULL, the brief supplies flags and n_layers; PACKED and DENSE records are refused).
+ *
+ * Per packet i the first rule that applies decides. Positions count from the layer's first byte (the UDP payload's
+ * first byte); d[x] is the byte at x, L the payload length:
+ *   1 BAD_DESC. offsets[i] + caplens[i] > data_len, the 64-bit wrap checked (pcppx_move.h's out_of_bounds): the packet
+ *     is never read.
+ *   2 Incomplete chain -> HOST: flags has PCPPX_F_NEEDS_HOST_PROTO, OVERSIZE, BAD_DESC or DEPTH_OVERFLOW, or n_layers >
+ *     max_layers, or NEEDS_HOST_L7 is set without L7_KNOWN.
+ *   3 No candidate -> NONE: NEEDS_HOST_L7 is clear, or one of L7_HTTP / L7_SSL / L7_DNS is set.
+ *   4 The carrier: the last entry k < n_layers whose proto is 5 (pcpp::UDP). It must be the last entry, or be followed
+ *     by one PacketTrailer (30) entry that is the last; hdr_len == 8 < data_len and offset + data_len <= caplen.
+ *     Otherwise NONE; a TCP carrier is NONE. L = data_len - 8; the ports are the header's bytes 0..3 (big-endian source,
+ *     destination).
+ *   5 The DHCP port pair (68->67, 67->68, 67->67; DhcpLayer.h:784-788): L >= 240 (isDataValid :594-597) -> a DHCPv4
+ *     message, whatever bytes 236..239 hold (the reference does not check the magic number); L < 240 -> NONE (the
+ *     Payload fallback).
+ *   6 Otherwise a DHCPv6 candidate needs a port 546 or 547 on either side; without one -> NONE. Destination port 4789,
+ *     or a port 5060 / 5061 on either side -> NONE (VXLAN and SIP come first and both fall back to a Payload,
+ *     UdpLayer.cpp:107-121). The other port one of 1812, 1813, 3799 (RADIUS), 2152, 2123 (GTP) -> HOST (whether that
+ *     dissector takes the payload is the host's answer). L >= 4 (DhcpV6Layer.h:393-396) -> a DHCPv6 message; L < 4 ->
+ *     NONE.
+ *   7 A message whose family is not in spec->families is NONE (the HOST verdicts of rules 2 and 6 come first).
+ *   8 The DHCPv4 options (getFirstTLVRecord / getNextTLVRecord over DhcpOption, DhcpLayer.h:452-492), from p = 240.
+ *     At each step, with rem = L - p: rem < 1 stops. t = d[p]. t == 0 (PAD) or t == 255 (END): the record is one byte
+ *     and its value length is 0. Otherwise rem < 2 stops; len = d[p + 1] and the record is 2 + len bytes. A record that
+ *     ends behind L stops the walk and is not counted; otherwise it is counted and p moves behind it. END does not end
+ *     the walk: trailing PAD bytes each count as an option, as getOptionsCount() counts them.
+ *   9 The DHCPv6 options (DhcpV6Layer.cpp:37-51), from p = 4: L - p < 4 stops; code = be16(d[p]), len = be16(d[p + 2]),
+ *     the record is 4 + len bytes; one that ends behind L stops the walk and is not counted. code is the two bytes as
+ *     they are (DhcpV6Option::getType() maps codes outside its enum to 0; the record keeps the number).
+ *  10 n_options is the count of rule 8 / 9 (getOptionsCount() / getOptionCount()) and options_len the bytes the counted
+ *     records cover, whatever spec->options says. A record is emitted per counted option with spec->options ALL, and
+ *     with WANTED per counted option whose code is wanted: bit c of want4 for DHCPv4 code c, a member of want6[0 ..
+ *     n_codes6) for DHCPv6. With spec->values each emitted option's value bytes go to out->values, in walk order.
+ *  11 Typed values, each from the first counted option of its code, whatever spec->options says. DHCPv4: msg_type is
+ *     option 53's first value byte, 0 when the option is absent or its length is 0 (getMessageType,
+ *     getValueAs<uint8_t>), HAS_MSG_TYPE when the option exists; lease_time is option 51's first four bytes big-endian
+ *     when its length is >= 4, else 0, HAS_LEASE_TIME when the option exists with such a length; server_id is option
+ *     54's first four bytes when its length is >= 4, else zeros, HAS_SERVER_ID likewise. client_mac is
+ *     getClientHardwareAddress(): bytes 28..33 when htype == 1 and hlen == 6 (HAS_MAC), else zeros. MAGIC_OK: bytes
+ *     236..239 are 63 82 53 63 (informational). REPLY: op == 2. DHCPv6: msg_type is d[0] when it is <= 13, else 0
+ *     (DhcpV6Layer.cpp:83-92); xid is getTransactionID() (bytes 1..3, big-endian); the DHCPv4-only fields are zero.
+ *  12 Source bytes are read only inside the UDP payload of in-bounds packets, plus the UDP header's four port bytes. */
+typedef struct pcppx_dhcp_spec { /* 72 bytes */
+	uint32_t max_msgs;   /* 0 = n */
+	uint8_t families;    /* bit 0 DHCPv4, bit 1 DHCPv6; 1..3 */
+	uint8_t options;     /* PCPPX_DHCP_OPTIONS_*: 0 NONE, 1 WANTED, 2 ALL (PAD / END included) */
+	uint8_t values;      /* 1: the emitted options' value bytes go to out->values */
+	uint8_t n_codes6;    /* <= PCPPX_DHCP_MAX_CODES6 */
+	uint32_t want4[8];   /* bit c of the 256 (word c / 32, bit c % 32): DHCPv4 code c is wanted */
+	uint16_t want6[16];  /* the wanted DHCPv6 codes, strictly ascending; 0 beyond n_codes6 */
+} pcppx_dhcp_spec;
+#define PCPPX_DHCP_V4 1 /* pcppx_dhcp_spec.families bits */
+#define PCPPX_DHCP_V6 2
+#define PCPPX_DHCP_OPTIONS_NONE 0
+#define PCPPX_DHCP_OPTIONS_WANTED 1
+#define PCPPX_DHCP_OPTIONS_ALL 2
+#define PCPPX_DHCP_MAX_CODES6 16
+
+typedef struct pcppx_dhcp_option { /* 16 bytes, message by message, in walk order */
+	uint32_t msg;        /* its message's record number in out->msgs */
+	uint16_t code;       /* getType(): d[p]; DHCPv6: be16(d[p]) */
+	uint16_t len;        /* getDataSize() */
+	uint16_t offset;     /* the record's first byte, from the layer's first byte */
+	uint16_t ordinal;    /* its number among all the message's counted options */
+	uint16_t value_rel;  /* its value's first byte in out->values, from the message's value_pos; 0 without values */
+	uint16_t reserved;   /* 0 */
+} pcppx_dhcp_option;
+
+/* pcppx_dhcp_msg.flags */
+#define PCPPX_DHCP_HAS_MSG_TYPE 1   /* option 53 was found */
+#define PCPPX_DHCP_HAS_MAC 2        /* htype == 1 and hlen == 6 */
+#define PCPPX_DHCP_MAGIC_OK 4       /* bytes 236..239 are 63 82 53 63 */
+#define PCPPX_DHCP_HAS_LEASE_TIME 8 /* option 51 with a length >= 4 */
+#define PCPPX_DHCP_HAS_SERVER_ID 16 /* option 54 with a length >= 4 */
+#define PCPPX_DHCP_REPLY 32         /* op == 2 */
+
+typedef struct pcppx_dhcp_msg { /* 80 bytes per DHCP / DHCPv6 packet, in source order */
+	uint64_t first_option; /* record number in out->options of its first option record */
+	uint64_t value_pos;    /* its first byte in out->values */
+	uint32_t index;        /* source packet number (strictly ascending) */
+	uint32_t xid;          /* DHCPv4: be32 of bytes 4..7; DHCPv6: getTransactionID() */
+	uint32_t lease_time;   /* rule 11 */
+	uint16_t layer_offset; /* the layer's first byte, from the packet's first byte */
+	uint16_t layer_len;    /* L */
+	uint16_t n_options;    /* getOptionsCount() / getOptionCount(), whatever spec->options says */
+	uint16_t n_rec;        /* the option records emitted for it */
+	uint16_t value_len;    /* the bytes it put into out->values */
+	uint16_t options_len;  /* the bytes the counted options cover */
+	uint16_t secs;         /* be16 of bytes 8..9 */
+	uint16_t bootp_flags;  /* be16 of bytes 10..11 */
+	uint8_t family;        /* 4 | 6 */
+	uint8_t msg_type;      /* rule 11 */
+	uint8_t flags;         /* PCPPX_DHCP_* above */
+	uint8_t op;            /* getOpCode(): byte 0 */
+	uint8_t htype, hlen, hops;
+	uint8_t reserved0;     /* 0 */
+	uint8_t ciaddr[4], yiaddr[4], siaddr[4], giaddr[4]; /* bytes 12..27, network order */
+	uint8_t server_id[4];  /* rule 11 */
+	uint8_t client_mac[6]; /* getClientHardwareAddress(): zeros unless htype 1, hlen 6 */
+	uint8_t reserved[2];   /* 0 */
+} pcppx_dhcp_msg;
+
+/* pcppx_dhcp_out.disposition values */
+#define PCPPX_DHCP_NONE 0     /* the reference builds no DHCP / DHCPv6 layer of a family in spec->families here */
+#define PCPPX_DHCP_MSG 1      /* a message record */
+#define PCPPX_DHCP_HOST 2     /* only the host can tell (rules 2 and 6) */
+#define PCPPX_DHCP_BAD_DESC 3 /* the descriptor is out of bounds: never read */
+
+/* pcppx_dhcp_out.totals words */
+#define PCPPX_DHCP_MSGS 0
+#define PCPPX_DHCP_V4_N 1
+#define PCPPX_DHCP_V6_N 2
+#define PCPPX_DHCP_OPTIONS 3        /* the option records emitted */
+#define PCPPX_DHCP_VALUE_BYTES 4
+#define PCPPX_DHCP_HOST_N 5
+#define PCPPX_DHCP_BAD_DESC_N 6
+#define PCPPX_DHCP_OPTIONS_LINKED 7 /* the sum of n_options */
+#define PCPPX_DHCP_REPLIES 8        /* messages with PCPPX_DHCP_REPLY */
+#define PCPPX_DHCP_OVERFLOW 9
+#define PCPPX_DHCP_TOTALS 10
+
+typedef struct pcppx_dhcp_out { /* device pointers; host pointers for pcppx_dhcp_reference */
+	pcppx_dhcp_msg* msgs;       /* max_msgs entries, in source order */
+	pcppx_dhcp_option* options; /* max_options entries: message by message, each in walk order */
+	uint8_t* values;            /* the emitted options' values back to back in record order; NULL = no bytes */
+	uint64_t values_cap;
+	uint8_t* disposition;       /* optional (NULL): n entries, PCPPX_DHCP_* per source packet */
+	uint32_t max_msgs;
+	uint32_t max_options;
+	uint64_t reserved;          /* 0 */
+	uint64_t* totals;           /* PCPPX_DHCP_TOTALS words, overwritten by each call (not accumulated) */
+} pcppx_dhcp_out;
+
+/* Capacity is all or nothing, as in sip: OVERFLOW = 1 iff MSGS > out->max_msgs, or OPTIONS > max_options, or values !=
+ * NULL and VALUE_BYTES > values_cap, or MSGS > spec->max_msgs (0 = n). Then only the totals are written (no record, no
+ * value byte, no disposition); they always hold the full would-be values. With values == NULL positions and lengths
+ * are still filled and the byte capacity is not applied. Sizing: a call with max_msgs = max_options = 0 overflows (when
+ * there is a message) and gives MSGS, OPTIONS and VALUE_BYTES. The cost of a message is linear in its payload's L
+ * bytes: the walk reads one or two bytes per option, and each emitted value byte is copied once.
+ * Nothing is written outside the first MSGS messages, the first OPTIONS records, [0, VALUE_BYTES) of values and the n
+ * dispositions. The output is a pure function of the inputs, bit-identical from run to run: positions come from counts
+ * and scans, and there are no atomics. n == 0 is legal (zero totals).
+ * PCPPX_E_INVAL before any device work: sip's list (a null ctx, batch, records, spec, out, totals or msgs; with n > 0 a
+ * null records->layers, or records->summary and records->brief both; PACKED or DENSE records; max_layers 0 or above
+ * PCPPX_MAX_LAYERS), plus families 0 or above 3; options above 2; values above 1; n_codes6 above 16; want6 not strictly
+ * ascending below n_codes6, or not 0 beyond; a null out->options; a non-zero out->reserved. The work is queued on
+ * hip_stream and the call returns without waiting; calls on one context are ordered through its dhcp scratch (a buffer
+ * and an event of their own, as sip's). Scratch: with g = ceil(n / 1024) blocks, 60 g + 16 n bytes (per block nine
+ * 32-bit sums -- its messages, option records, value bytes, DHCPv4 and DHCPv6 messages, HOST and BAD_DESC packets,
+ * linked options and replies -- and the 64-bit exclusive prefixes of the first three; per packet a 16-byte plan: the
+ * layer's offset and length, the family, the records and value bytes of the message, its option count, whether it is a
+ * reply, and the disposition); PCPPX_E_NOMEM when it cannot be allocated. */
+PCPPX_API int pcppx_dhcp_device(pcppx_ctx* ctx, const pcppx_batch* batch, const pcppx_records* records,
+                                uint8_t max_layers, const pcppx_dhcp_spec* spec, pcppx_dhcp_out* out, void* hip_stream);
+/* The same contract in plain C++ over host pointers (no GPU, no context): what a host caller uses. */
+PCPPX_API int pcppx_dhcp_reference(const pcppx_batch* batch, const pcppx_records* records, uint8_t max_layers,
+                                   const pcppx_dhcp_spec* spec, pcppx_dhcp_out* out);
+
 /* ---- bpf: classic BPF filter programs run over the packets of a device batch (the capture-side filter step) ----
  * The reference's users choose packets with pcap filters: IFileReaderDevice::setFilter,
  * BpfFilterWrapper::matchPacketWithFilter and the GeneralFilter family (Pcap++/src/PcapFilter.cpp) all end in

@@ -730,6 +730,93 @@ def sip_reference(batch: Batch, records: Records, max_layers: int, spec: HttpSpe
                                             C.byref(out)), "pcppx_sip_reference")
 
 
+# pcppx_dhcp_*: the DHCP and DHCPv6 messages and their options of a batch (include/pcppx.h, dhcp)
+DHCP_NONE, DHCP_MSG, DHCP_HOST, DHCP_BAD_DESC = range(4)  # disposition
+DHCP_V4, DHCP_V6 = 1, 2                                   # spec.families bits
+DHCP_OPTIONS_NONE, DHCP_OPTIONS_WANTED, DHCP_OPTIONS_ALL = 0, 1, 2  # spec.options
+DHCP_MAX_CODES6 = 16
+(DHCP_HAS_MSG_TYPE, DHCP_HAS_MAC, DHCP_MAGIC_OK, DHCP_HAS_LEASE_TIME, DHCP_HAS_SERVER_ID,
+ DHCP_REPLY) = 1, 2, 4, 8, 16, 32  # msg.flags
+(DHCP_MSGS, DHCP_V4_N, DHCP_V6_N, DHCP_OPTIONS, DHCP_VALUE_BYTES, DHCP_HOST_N, DHCP_BAD_DESC_N, DHCP_OPTIONS_LINKED,
+ DHCP_REPLIES, DHCP_OVERFLOW) = range(10)  # pcppx_dhcp_out.totals
+DHCP_TOTALS = 10
+DHCP_TOTAL_NAMES = ("msgs", "v4", "v6", "options", "value_bytes", "host_n", "bad_desc", "options_linked", "replies",
+                    "overflow")
+DHCP_MSG_TYPES = ("UNKNOWN", "DISCOVER", "OFFER", "REQUEST", "DECLINE", "ACK", "NAK", "RELEASE", "INFORM")  # DHCPv4
+DHCP_MSG_DTYPE = np.dtype(
+    [("first_option", "<u8"), ("value_pos", "<u8"), ("index", "<u4"), ("xid", "<u4"), ("lease_time", "<u4"),
+     ("layer_offset", "<u2"), ("layer_len", "<u2"), ("n_options", "<u2"), ("n_rec", "<u2"), ("value_len", "<u2"),
+     ("options_len", "<u2"), ("secs", "<u2"), ("bootp_flags", "<u2"), ("family", "u1"), ("msg_type", "u1"),
+     ("flags", "u1"), ("op", "u1"), ("htype", "u1"), ("hlen", "u1"), ("hops", "u1"), ("reserved0", "u1"),
+     ("ciaddr", "u1", (4,)), ("yiaddr", "u1", (4,)), ("siaddr", "u1", (4,)), ("giaddr", "u1", (4,)),
+     ("server_id", "u1", (4,)), ("client_mac", "u1", (6,)), ("reserved", "u1", (2,))]
+)
+DHCP_OPTION_DTYPE = np.dtype(
+    [("msg", "<u4"), ("code", "<u2"), ("len", "<u2"), ("offset", "<u2"), ("ordinal", "<u2"), ("value_rel", "<u2"),
+     ("reserved", "<u2")]
+)
+assert DHCP_MSG_DTYPE.itemsize == 80 and DHCP_OPTION_DTYPE.itemsize == 16
+
+
+class DhcpSpec(C.Structure):
+    """pcppx_dhcp_spec: the room for messages (0 = n), the families, which options get records and whether their
+    values are copied, the wanted DHCPv4 codes as a 256-bit mask and the wanted DHCPv6 codes in ascending order."""
+    _fields_ = [("max_msgs", C.c_uint32), ("families", C.c_uint8), ("options", C.c_uint8), ("values", C.c_uint8),
+                ("n_codes6", C.c_uint8), ("want4", C.c_uint32 * 8), ("want6", C.c_uint16 * 16)]
+
+
+class DhcpOption(C.Structure):
+    """pcppx_dhcp_option (DHCP_OPTION_DTYPE is its numpy mirror)."""
+    _fields_ = [("msg", C.c_uint32), ("code", C.c_uint16), ("len", C.c_uint16), ("offset", C.c_uint16),
+                ("ordinal", C.c_uint16), ("value_rel", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class DhcpMsg(C.Structure):
+    """pcppx_dhcp_msg (DHCP_MSG_DTYPE is its numpy mirror)."""
+    _fields_ = [("first_option", C.c_uint64), ("value_pos", C.c_uint64), ("index", C.c_uint32), ("xid", C.c_uint32),
+                ("lease_time", C.c_uint32), ("layer_offset", C.c_uint16), ("layer_len", C.c_uint16),
+                ("n_options", C.c_uint16), ("n_rec", C.c_uint16), ("value_len", C.c_uint16),
+                ("options_len", C.c_uint16), ("secs", C.c_uint16), ("bootp_flags", C.c_uint16), ("family", C.c_uint8),
+                ("msg_type", C.c_uint8), ("flags", C.c_uint8), ("op", C.c_uint8), ("htype", C.c_uint8),
+                ("hlen", C.c_uint8), ("hops", C.c_uint8), ("reserved0", C.c_uint8), ("ciaddr", C.c_uint8 * 4),
+                ("yiaddr", C.c_uint8 * 4), ("siaddr", C.c_uint8 * 4), ("giaddr", C.c_uint8 * 4),
+                ("server_id", C.c_uint8 * 4), ("client_mac", C.c_uint8 * 6), ("reserved", C.c_uint8 * 2)]
+
+
+class DhcpOut(C.Structure):
+    """pcppx_dhcp_out: the messages, the option records, the values back to back, the disposition and the totals."""
+    _fields_ = [("msgs", C.c_void_p), ("options", C.c_void_p), ("values", C.c_void_p), ("values_cap", C.c_uint64),
+                ("disposition", C.c_void_p), ("max_msgs", C.c_uint32), ("max_options", C.c_uint32),
+                ("reserved", C.c_uint64), ("totals", C.c_void_p)]
+
+
+DHCP_ASSET_CODES4 = (12, 50, 51, 53, 54, 55, 60, 61)  # host name, requested address, lease, type, server, lists, ids
+DHCP_ASSET_CODES6 = (1, 2, 3, 39)                     # client id, server id, IA_NA, client FQDN
+
+
+def make_dhcp_spec(codes4=DHCP_ASSET_CODES4, codes6=DHCP_ASSET_CODES6, options: int = DHCP_OPTIONS_WANTED,
+                   values: int = 1, families: int = 3, max_msgs: int = 0) -> DhcpSpec:
+    """codes4: wanted DHCPv4 codes 0..255; codes6: up to 16 wanted DHCPv6 codes, written as given (the call refuses a
+    list that is not strictly ascending)."""
+    s = DhcpSpec(max_msgs, families, options, values, min(len(codes6), 255))
+    for c in codes4:
+        s.want4[(c & 255) >> 5] |= 1 << (c & 31)
+    for k, c in enumerate(codes6[:DHCP_MAX_CODES6]):
+        s.want6[k] = c
+    return s
+
+
+def dhcp_totals_dict(totals) -> dict:
+    return {f: int(totals[k]) for k, f in enumerate(DHCP_TOTAL_NAMES)}
+
+
+def dhcp_reference(batch: Batch, records: Records, max_layers: int, spec: DhcpSpec, out: DhcpOut) -> None:
+    """pcppx_dhcp_reference: pcppx_dhcp_device's contract in plain C++ over host pointers (no GPU). The structs hold
+    addresses of host (numpy) arrays the caller keeps alive; out's arrays and totals are filled in place."""
+    check(load_engine().pcppx_dhcp_reference(C.byref(batch), C.byref(records), max_layers, C.byref(spec),
+                                             C.byref(out)), "pcppx_dhcp_reference")
+
+
 # pcppx_bpf_*: classic BPF programs over a batch (include/pcppx.h, bpf)
 BPF_MAX_INSNS, BPF_MAX_PROGRAMS, BPF_MEMWORDS = 4096, 16, 16
 BPF_MATCHED, BPF_BAD_DESC = 0, 1  # pcppx_bpf_verdicts.totals words (PCPPX_BPF_*)
@@ -996,6 +1083,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.pcppx_sip_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(HttpSpec),
                                         C.POINTER(SipOut)]
     lib.pcppx_sip_reference.restype = C.c_int
+    lib.pcppx_dhcp_device.argtypes = [P, C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(DhcpSpec),
+                                      C.POINTER(DhcpOut), P]
+    lib.pcppx_dhcp_device.restype = C.c_int
+    lib.pcppx_dhcp_reference.argtypes = [C.POINTER(Batch), C.POINTER(Records), C.c_uint8, C.POINTER(DhcpSpec),
+                                         C.POINTER(DhcpOut)]
+    lib.pcppx_dhcp_reference.restype = C.c_int
     lib.pcppx_bpf_validate.argtypes = [P, C.c_uint32]
     lib.pcppx_bpf_validate.restype = C.c_int
     lib.pcppx_bpf_load.argtypes = [P, P, C.c_uint32, C.POINTER(P)]
@@ -1029,6 +1122,7 @@ EXPORTED_SYMBOLS = (
     "pcppx_http_device", "pcppx_http_reference",
     "pcppx_ssl_device", "pcppx_ssl_reference",
     "pcppx_sip_device", "pcppx_sip_reference",
+    "pcppx_dhcp_device", "pcppx_dhcp_reference",
     "pcppx_bpf_validate", "pcppx_bpf_load", "pcppx_bpf_free", "pcppx_bpf_device", "pcppx_bpf_reference",
 )
 

@@ -1,6 +1,6 @@
 // pcppx_args.h — the argument rules that the message operators' valid_args (pcppx_tlsfp.h, pcppx_dns.h, pcppx_http.h,
-// pcppx_ssl.h; sip delegates to http) begin and end with. Plain C++ without HIP: the *_ref.cpp files compile it with a
-// host compiler alone.
+// pcppx_ssl.h, pcppx_dhcp.h; sip delegates to http) begin and end with. Plain C++ without HIP: the *_ref.cpp files
+// compile it with a host compiler alone.
 #pragma once
 
 #include <stdint.h>

@@ -23,6 +23,7 @@
 #include "pcppx_dns.h"
 #include "pcppx_http.h"
 #include "pcppx_sip.h"
+#include "pcppx_dhcp.h"
 #include "pcppx_ssl.h"
 
 namespace
@@ -252,9 +253,9 @@ struct pcppx_ctx
 	Scratch tcpstream;
 	// pcppx_frag_device: the block sums and bases and the per-packet plans (frag_scratch_bytes)
 	Scratch frag;
-	// pcppx_tlsfp_device, pcppx_dns_device, pcppx_http_device, pcppx_ssl_device, pcppx_sip_device: each one's per-packet
-	// plans and block sums and bases (<op>_scratch_bytes)
-	Scratch tlsfp, dns, http, ssl, sip;
+	// pcppx_tlsfp_device, pcppx_dns_device, pcppx_http_device, pcppx_ssl_device, pcppx_sip_device, pcppx_dhcp_device:
+	// each one's per-packet plans and block sums and bases (<op>_scratch_bytes)
+	Scratch tlsfp, dns, http, ssl, sip, dhcp;
 	// the engine's header-window choice for PCPPX_WINDOW_DEFAULT launches: a sampled parse (every launch until the first
 	// decision, then one in kWinEvery) first adds the live packets and deep stacks of about 64 of its tiles to d_win (never
 	// cleared); after it, a private stream copies the counters into a page-locked mirror, which a later launch reads once
@@ -945,6 +946,8 @@ extern "C"
 		c->ssl.release(c->stream);
 		c->sip.wait();
 		c->sip.release(c->stream);
+		c->dhcp.wait();
+		c->dhcp.release(c->stream);
 		(void)hipStreamSynchronize(c->stream);
 		if (c->win_ready)
 		{
@@ -956,7 +959,7 @@ extern "C"
 			(void)hipHostFree(c->h_win);
 		}
 		for (const Scratch* x : { &c->flow, &c->stats, &c->select, &c->steer, &c->defrag, &c->tcpstream, &c->frag,
-		                         &c->tlsfp, &c->dns, &c->http, &c->ssl, &c->sip })
+		                         &c->tlsfp, &c->dns, &c->http, &c->ssl, &c->sip, &c->dhcp })
 			x->destroy_event();
 		(void)hipStreamDestroy(c->stream);
 		delete c;
@@ -1858,11 +1861,11 @@ extern "C"
 	}
 }
 
-// ---- the message operators: tlsfp, dns, http, ssl, sip (include/pcppx.h) ----
+// ---- the message operators: tlsfp, dns, http, ssl, sip, dhcp (include/pcppx.h) ----
 // pcppx_<op>_reference is pcppx_<op>_ref.cpp (plain C++); the argument rules both calls share are pcppx_<op>.h's
 namespace
 {
-// What the five device entries do once the arguments have their verdict (valid: with c there). scratch: the context's
+// What the six device entries do once the arguments have their verdict (valid: with c there). scratch: the context's
 // own for the operator, which its previous call (possibly queued on another stream) owns until it is done.
 template <class Spec, class Out>
 int message_device(pcppx_ctx* c, bool valid, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
@@ -1931,6 +1934,14 @@ extern "C"
 		return message_device<pcppx_sip_spec, pcppx_sip_out>(
 		    c, c != nullptr && pcppx::sip::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o, PCPPX_SIP_TOTALS,
 		    &pcppx_ctx::sip, pcppx::sip_scratch_bytes, pcppx::launch_sip, hip_stream);
+	}
+
+	int pcppx_dhcp_device(pcppx_ctx* c, const pcppx_batch* b, const pcppx_records* r, uint8_t max_layers,
+	                      const pcppx_dhcp_spec* s, pcppx_dhcp_out* o, void* hip_stream)
+	{
+		return message_device<pcppx_dhcp_spec, pcppx_dhcp_out>(
+		    c, c != nullptr && pcppx::dhcp::valid_args(b, r, max_layers, s, o), b, r, max_layers, s, o, PCPPX_DHCP_TOTALS,
+		    &pcppx_ctx::dhcp, pcppx::dhcp_scratch_bytes, pcppx::launch_dhcp, hip_stream);
 	}
 }
 

@@ -96,25 +96,28 @@ uint64_t frag_scratch_bytes(uint32_t n);
 int launch_frag(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* n_layers,
                 uint32_t nl_stride, const pcppx_frag6_spec* spec, const pcppx_fragmented* out, void* scratch,
                 hipStream_t stream);
-// The message operators pcppx_tlsfp_device, pcppx_dns_device, pcppx_http_device, pcppx_ssl_device and pcppx_sip_device
-// (pcppx_<op>.hip): three launches on `stream` each (plan, bases, emit). scratch: <op>_scratch_bytes(n) bytes
-// (include/pcppx.h gives the formulas); one block takes k<Op>BlockPk source packets and writes their records; rec0:
+// The message operators pcppx_tlsfp_device, pcppx_dns_device, pcppx_http_device, pcppx_ssl_device, pcppx_sip_device and
+// pcppx_dhcp_device (pcppx_<op>.hip): three launches on `stream` each (plan, bases, emit). scratch:
+// <op>_scratch_bytes(n) bytes (include/pcppx.h gives the formulas); one block takes k<Op>BlockPk source packets and writes their records; rec0:
 // packet 0's summary or brief, rec_stride bytes apart. Arguments are checked by the caller; n > 0.
 constexpr uint32_t kTlsfpBlockPk = 1024;
 constexpr uint32_t kDnsBlockPk = 1024;
 constexpr uint32_t kHttpBlockPk = 1024;
 constexpr uint32_t kSslBlockPk = 1024;
 constexpr uint32_t kSipBlockPk = 1024;
+constexpr uint32_t kDhcpBlockPk = 1024;
 uint32_t tlsfp_blocks(uint32_t n);
 uint32_t dns_blocks(uint32_t n);
 uint32_t http_blocks(uint32_t n);
 uint32_t ssl_blocks(uint32_t n);
 uint32_t sip_blocks(uint32_t n);
+uint32_t dhcp_blocks(uint32_t n);
 uint64_t tlsfp_scratch_bytes(uint32_t n);
 uint64_t dns_scratch_bytes(uint32_t n);
 uint64_t http_scratch_bytes(uint32_t n);
 uint64_t ssl_scratch_bytes(uint32_t n);
 uint64_t sip_scratch_bytes(uint32_t n);
+uint64_t dhcp_scratch_bytes(uint32_t n);
 int launch_tlsfp(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
                  const pcppx_tlsfp_spec* spec, const pcppx_tlsfps* out, void* scratch, hipStream_t stream);
 int launch_dns(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
@@ -125,6 +128,8 @@ int launch_ssl(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, con
                const pcppx_ssl_spec* spec, const pcppx_ssl_out* out, void* scratch, hipStream_t stream);
 int launch_sip(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
                const pcppx_sip_spec* spec, const pcppx_sip_out* out, void* scratch, hipStream_t stream);
+int launch_dhcp(const pcppx_batch* b, const pcppx_layer* layers, uint32_t ml, const uint8_t* rec0, uint32_t rec_stride,
+                const pcppx_dhcp_spec* spec, const pcppx_dhcp_out* out, void* scratch, hipStream_t stream);
 // pcppx_bpf_device (pcppx_bpf.hip): one launch on `stream` (the caller has cleared out->totals on it). insns: the
 // validated programs back to back in device memory; program p is insns[start[p] .. start[p + 1]); uses_mem: bit p set
 // when program p loads from M[] (only then are its slots cleared). Arguments are checked by the caller; n > 0.

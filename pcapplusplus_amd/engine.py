@@ -355,6 +355,22 @@ class Engine:
         abi.check(self.lib.pcppx_sip_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_sip_device")
 
+    def dhcp_device(self, data, offsets, caplens, n: int, linktype: int, layers, max_layers: int, spec: abi.DhcpSpec,
+                    msgs, options, totals, max_msgs: int, max_options: int, values=None, values_cap: int = 0,
+                    disposition=None, stream: int | None = None, data_len: int | None = None, summary=None,
+                    brief=None) -> None:
+        """Queue pcppx_dhcp_device over device tensors: one message (abi.DHCP_MSG_DTYPE, 80 bytes) per DHCP / DHCPv6
+        packet and one record (abi.DHCP_OPTION_DTYPE, 16 bytes) per option spec asks for, with the value bytes spec
+        asks for. summary (n * 32 bytes) or brief (n * 16 bytes): the parse's records, one of them; layers: FIXED,
+        n * max_layers * 8 bytes. msgs: max_msgs * 80 bytes; options: max_options * 16 bytes; values (u8, values_cap
+        bytes; None = positions only); disposition (u8[n], optional); totals: 10 x i64 (abi.DHCP_*), overwritten. All
+        or nothing: on overflow only the totals are written. Returns without waiting."""
+        b, rec = _source(data, offsets, caplens, n, linktype, layers, summary, brief, data_len)
+        out = abi.DhcpOut(abi.ptr(msgs), abi.ptr(options), _opt(values), values_cap, _opt(disposition), max_msgs,
+                          max_options, 0, abi.ptr(totals))
+        abi.check(self.lib.pcppx_dhcp_device(self.ctx, C.byref(b), C.byref(rec), max_layers, C.byref(spec),
+                                             C.byref(out), C.c_void_p(stream or 0)), "pcppx_dhcp_device")
+
     def bpf_load(self, programs) -> "BpfFilter":
         """pcppx_bpf_load: validate 1..16 classic BPF programs (abi.BPF_INSN_DTYPE arrays or (code, jt, jf, k) rows; see
         pcapplusplus_amd.bpf) and copy them to this context's GPU. Raises on a program the validator refuses."""
@@ -1109,6 +1125,45 @@ def sip_on_device(eng: Engine, batch: PacketBatch, spec: abi.SipSpec | None = No
     return (msgs.cpu().numpy().view(abi.SIP_MSG_DTYPE)[:m], fields.cpu().numpy().view(abi.SIP_FIELD_DTYPE)[:k],
             sdps.cpu().numpy().view(abi.SIP_SDP_DTYPE)[:ns],
             text[:nb].cpu().numpy() if want_text else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
+
+
+def dhcp_on_device(eng: Engine, batch: PacketBatch, spec: abi.DhcpSpec | None = None, opts: abi.Opts | None = None,
+                   want_values: bool = True, device: str = "cuda:0"):
+    """Copy a host batch to HBM, parse it there and walk its DHCP / DHCPv6 messages (pcppx_dhcp_device) without the
+    records leaving the device in between; copy the result back: (msgs abi.DHCP_MSG_DTYPE[m] in source order, options
+    abi.DHCP_OPTION_DTYPE[k] message by message, values u8 = the value bytes spec asks for back to back (empty with
+    want_values = False), disposition u8[n] = abi.DHCP_* per source packet, totals dict). spec None: the asset
+    discovery options (abi.DHCP_ASSET_CODES4 / 6) with their values. The buffers are sized by a first call without
+    room, which overflows (where there is a message) and writes the totals alone."""
+    import torch
+
+    opts = opts or abi.make_opts()
+    spec = spec or abi.make_dhcp_spec()
+    n, ml = batch.n, opts.max_layers
+    data, offsets, caplens = to_device(batch, device)
+    summary = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=device)
+    layers = torch.zeros(max(n * ml, 1) * 8, dtype=torch.uint8, device=device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    eng.parse_device(data, offsets, caplens, n, batch.linktype, opts, summary, layers, st)
+    totals = torch.empty(abi.DHCP_TOTALS, dtype=torch.int64, device=device)
+
+    def call(msgs, max_msgs, options, max_options, values=None, cap=0, disp=None):
+        eng.dhcp_device(data, offsets, caplens, n, batch.linktype, layers, ml, spec, msgs, options, totals, max_msgs,
+                        max_options, values, cap, disp, st, summary=summary)
+        torch.cuda.synchronize(device)
+        return abi.dhcp_totals_dict(totals.cpu().numpy().view(np.uint64))
+
+    one = torch.empty(80, dtype=torch.uint8, device=device)
+    need = call(one, 0, one, 0)
+    m, k, nb = need["msgs"], need["options"], need["value_bytes"]
+    msgs = torch.empty(max(m, 1) * 80, dtype=torch.uint8, device=device)
+    options = torch.empty(max(k, 1) * 16, dtype=torch.uint8, device=device)
+    values = torch.empty(max(nb, 1), dtype=torch.uint8, device=device) if want_values else None
+    disp = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    tot = call(msgs, m, options, k, values, nb, disp)
+    assert tot["overflow"] == 0
+    return (msgs.cpu().numpy().view(abi.DHCP_MSG_DTYPE)[:m], options.cpu().numpy().view(abi.DHCP_OPTION_DTYPE)[:k],
+            values[:nb].cpu().numpy() if want_values else np.zeros(0, np.uint8), disp[:n].cpu().numpy(), tot)
 
 
 def bpf_on_device(eng: Engine, batch: PacketBatch, programs, frame_lens=None, device: str = "cuda:0"):
