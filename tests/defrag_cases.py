@@ -558,8 +558,10 @@ def cases() -> list[Case]:
                                                            trailer=b"\0" * 6)[::-1]], 9))))
     out.append(_clean(make("vlan", spread(rng, [group(rng, 0x433, [24, 8, 8, 1], vlan=100)], 11))))
     out.append(_clean(make("gre", spread(rng, [gre_group(rng, 0x434, [16, 24, 12])], 9))))
-    # crafted info: unrelated packets under one key merge as in the reference; keys congruent modulo the table size;
-    # key 0; the FRAGMENT status on a packet without an IPv4 layer
+    # crafted info: unrelated packets under one key merge as in the reference; keys congruent modulo every table size
+    # up to 1024 and key 0 (key 0 beside other keys is what that case reaches: the home slot comes from the high bits of
+    # key * 0x9E3779B1, so congruent keys land on scattered slots like any others; the probe chains, wraps and races are
+    # aimed at by tests/table_cases.py); the FRAGMENT status on a packet without an IPv4 layer
     a, b = group(rng, 0x440, [16, 7], src=0x0A000011), group(rng, 0x441, [16, 16, 3], src=0x0A000012)
     c = make("same_key_two_groups", spread(rng, [a, b], 12))  # two first fragments under one key: not a tiling
     c.info["ip_key"][c.info["ip_status"] & 15 == abi.IPR_FRAGMENT] = 0xDEADBEEF
@@ -574,7 +576,8 @@ def cases() -> list[Case]:
     for i in range(c.n):
         if int(c.info["ip_status"][i]) & 15 == abi.IPR_FRAGMENT:
             j = keys[int(c.info["ip_key"][i])]
-            c.info["ip_key"][i] = 5 + j * 1024 if j else 0  # one residue modulo every table size up to 1024; key 0
+            c.info["ip_key"][i] = 5 + j * 1024 if j else 0  # one residue modulo every table size up to 1024 (not one
+            # home slot: see above); key 0
     out.append(_clean(c))
     c = make("fragment_status_without_ipv4", spread(rng, [ok], 10, extra={3: eth(ethertype=0x0806) + bytes(28)}))
     c.info["ip_status"][3] = abi.IPR_FRAGMENT | abi.IPR_F_FIRST

@@ -8,11 +8,13 @@ fragmenter; it reproduces the reference's own IPFragUtil vectors (tests/golden/i
 frag -> parse -> defrag through the three host references gives the batch back.
 GPU: pcppx_frag_device equals pcppx_frag_reference byte for byte on the same cases; two calls on two streams agree and
 a repeat is bit-identical; source packets on both sides of offset 2^32; the reference's vectors on the device; frag ->
-parse + reasm -> defrag, all on the device, is the identity; fragmenting the fragments again changes nothing.
+parse + reasm -> defrag, all on the device, is the identity; fragmenting the fragments again changes nothing; a batch of
+more blocks than one step of the base scan takes, and defrag on the device over its fragments.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import re
 import subprocess
 import tempfile
@@ -502,3 +504,45 @@ def test_gpu_fragmenting_the_fragments_changes_nothing(engine):
     assert (disp[frags] == abi.FRAG_ALREADY).all() and (index == np.arange(b.n)).all() and not frag_no.any()
     assert (out.offsets == b.offsets).all() and (out.caplens == b.caplens).all()
     assert bytes(out.data) == bytes(b.data[:int(b.caplens.sum())])
+
+
+# ---------------------------------------------------------------- the base scan's second step
+N_WIDE, STEP = 66 * fc.BLOCK + 7, 64  # blocks a step of the base kernel takes
+WIDE_TOTALS = {"out_packets": 115881, "out_bytes": 15776646, "split_packets": 8958, "fragments": 57248,
+               "copied": 58633, "under_size": 53688}  # frozen; none is zero: every carried sum is used
+
+
+@functools.lru_cache(maxsize=None)
+def wide():
+    """(the 67-block case, what the reference leaves): built once, shared by the CPU and the GPU test."""
+    case = fc.make("wide", fc.mixed(np.random.default_rng(31), N_WIDE), frag_size=128)
+    return case, fc.run_reference(case)
+
+
+def test_reference_past_64_blocks():
+    case, want = wide()
+    assert case.n == N_WIDE and (N_WIDE + fc.BLOCK - 1) // fc.BLOCK == STEP + 3
+    fc.assert_same(want, fc.brute(case), "wide")
+    totals = abi.frag_totals_dict(want.totals)
+    assert totals["overflow"] == 0 and totals["bad_desc"] == 0
+    cnt = want.counts[:N_WIDE].astype(np.int64)
+    split = want.disposition[:N_WIDE] == abi.FRAG_SPLIT
+    for blk in (STEP, STEP + 1):  # the blocks behind the step line put packets out, fragments among them
+        rows = slice(blk * fc.BLOCK, (blk + 1) * fc.BLOCK)
+        assert int(cnt[rows].sum()) > fc.BLOCK and int(split[rows].sum()) >= 1, blk
+    assert all(v != 0 for v in WIDE_TOTALS.values()) and {k: totals[k] for k in WIDE_TOTALS} == WIDE_TOTALS
+
+
+@pytest.mark.gpu
+def test_gpu_frag_past_64_blocks(engine):
+    """The device equals the reference; and defrag on the device over the fragmented batch, whose groups then lie on
+    both sides of the step line of defrag's own scan, equals defrag's reference."""
+    case, want = wide()
+    got = fc.run_device(engine, case)
+    fc.assert_same(got, want, "wide")
+    back = defrag_case_of(fc.output_batch(got))
+    ref = dc.run_reference(back)
+    t = abi.defrag_totals_dict(ref.totals)
+    assert back.n == WIDE_TOTALS["out_packets"] > (STEP + 1) * dc.BLOCK and t["overflow"] == 0
+    assert t["reassembled"] > 8000 and t["out_packets"] > (STEP + 1) * dc.BLOCK
+    dc.assert_same(dc.run_device(engine, back), ref, "wide, defragmented")

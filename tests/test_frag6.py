@@ -9,11 +9,13 @@ case of tests/frag_cases.py; both models reproduce the fragments recorded from t
 reference's reassembly predicts, and the packets themselves where that can hold.
 GPU: pcppx_frag6_device equals pcppx_frag6_reference byte for byte on the same cases, the gap of an IPv6 fragment at
 every destination residue mod 16 among them; families = V4 is pcppx_frag_device bit for bit; two streams and a repeat
-agree; a source on both sides of offset 2^32; frag6 -> parse + reasm -> defrag6, all on the device.
+agree; a source on both sides of offset 2^32; frag6 -> parse + reasm -> defrag6, all on the device; a batch of more
+blocks than one step of the base scan takes, and defrag6 on the device over its fragments.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import re
 import subprocess
 import tempfile
@@ -657,3 +659,45 @@ def test_gpu_fragmenting_the_fragments_changes_nothing(engine):
     assert tot["split_packets"] == 0 and tot["overflow"] == 0 and out.n == b.n and frags.sum() > 500
     assert (disp[frags] == abi.FRAG_ALREADY).all() and (index == np.arange(b.n)).all() and not frag_no.any()
     assert bytes(out.data) == bytes(b.data[:int(b.caplens.sum())])
+
+
+# ---------------------------------------------------------------- the base scan's second step
+N_WIDE, STEP = 66 * fc.BLOCK + 7, 64  # blocks a step of the base kernel takes
+WIDE_TOTALS = {"out_packets": 127180, "out_bytes": 19350162, "split_packets": 11511, "fragments": 71100,
+               "copied": 56080, "under_size": 52372}  # frozen; none is zero: every carried sum is used
+
+
+@functools.lru_cache(maxsize=None)
+def wide():
+    """(the 67-block case, what the reference leaves): built once, shared by the CPU and the GPU test."""
+    case = f6.make("wide", f6.mixed(np.random.default_rng(32), N_WIDE), frag_size=128, id_base=7)
+    return case, f6.run_reference(case)
+
+
+def test_reference_past_64_blocks():
+    case, want = wide()
+    assert case.n == N_WIDE and (N_WIDE + fc.BLOCK - 1) // fc.BLOCK == STEP + 3
+    f6.assert_same(want, f6.brute(case), "wide")
+    totals = abi.frag_totals_dict(want.totals)
+    assert totals["overflow"] == 0 and totals["bad_desc"] == 0
+    cnt = want.counts[:N_WIDE].astype(np.int64)
+    split = want.disposition[:N_WIDE] == abi.FRAG_SPLIT
+    for blk in (STEP, STEP + 1):  # the blocks behind the step line put packets out, fragments among them
+        rows = slice(blk * fc.BLOCK, (blk + 1) * fc.BLOCK)
+        assert int(cnt[rows].sum()) > fc.BLOCK and int(split[rows].sum()) >= 1, blk
+    assert all(v != 0 for v in WIDE_TOTALS.values()) and {k: totals[k] for k in WIDE_TOTALS} == WIDE_TOTALS
+
+
+@pytest.mark.gpu
+def test_gpu_frag6_past_64_blocks(engine):
+    """The device equals the reference; and defrag6 on the device over the fragmented batch, whose groups then lie on
+    both sides of the step line of defrag's own scan, equals defrag6's reference."""
+    case, want = wide()
+    got = f6.run_device(engine, case)
+    f6.assert_same(got, want, "wide")
+    back = defrag6_case_of(f6.output_batch(got))
+    ref = d6.run_reference(back)
+    t = abi.defrag_totals_dict(ref.totals)
+    assert back.n == WIDE_TOTALS["out_packets"] > (STEP + 1) * dc.BLOCK and t["overflow"] == 0
+    assert t["reassembled"] > 8000 and t["out_packets"] > (STEP + 1) * dc.BLOCK
+    d6.assert_same(d6.run_device(engine, back), ref, "wide, defragmented")

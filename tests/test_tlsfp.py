@@ -8,11 +8,13 @@ output files (tests/golden/tlsfp) and agrees with the model on the bundled TLS c
 every length 0..130; and it runs clean under ASan + UBSan in a stand-alone program.
 GPU: pcppx_tlsfp_device equals pcppx_tlsfp_reference byte for byte on the same cases; two calls on two streams agree and
 a repeat is bit-identical; hello packets on both sides of offset 2^32; the golden files from a device parse, through the
-library and through tools/tlsfp_file.py; the records' MD5 words as pcppx_steer_device's key column.
+library and through tools/tlsfp_file.py; the records' MD5 words as pcppx_steer_device's key column; a batch of more
+blocks than one step of the base scan takes.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import hashlib
 import ipaddress
 import re
@@ -573,3 +575,34 @@ def test_gpu_md5_words_steer_equal_fingerprints_together(engine):
     table = tf.top(recs, abi.TLSFP_CLIENT, None) + tf.top(recs, abi.TLSFP_SERVER, None)
     # ch_k() of the odd packet numbers takes 20 of its 40 cipher values, sh_k() of the even ones its 7
     assert dict(table) == seen and len(seen) == 20 + 7 and sum(seen.values()) == k
+
+
+# ---------------------------------------------------------------- the base scan's second step
+N_WIDE, STEP = 66 * tc.BLOCK + 7, 64  # blocks a step of the base kernel takes
+WIDE_TOTALS = {"client_n": 22531, "server_n": 22530, "text_bytes": 1441969, "candidates": 45061}  # frozen; none is zero
+
+
+@functools.lru_cache(maxsize=None)
+def wide():
+    """(the 67-block case, what the reference leaves): built once, shared by the CPU and the GPU test."""
+    case = tc.make("wide", tc.mixed(N_WIDE))
+    return case, tc.run_reference(case)
+
+
+def test_reference_past_64_blocks():
+    case, want = wide()
+    assert case.n == N_WIDE and (N_WIDE + tc.BLOCK - 1) // tc.BLOCK == STEP + 3
+    tc.assert_same(want, tc.model(case), "wide")
+    totals = abi.tlsfp_totals_dict(want.totals)
+    assert totals["overflow"] == 0 and totals["host_n"] == 0 and totals["bad_desc"] == 0
+    disp = want.disposition[:N_WIDE]
+    for blk in (STEP, STEP + 1):  # the blocks behind the step line hold hellos of both kinds
+        rows = disp[blk * tc.BLOCK:(blk + 1) * tc.BLOCK]
+        assert len({int(d) for d in rows} - {tc.NONE, tc.HOST, tc.BAD}) == 2, blk
+    assert all(v != 0 for v in WIDE_TOTALS.values()) and {k: totals[k] for k in WIDE_TOTALS} == WIDE_TOTALS
+
+
+@pytest.mark.gpu
+def test_gpu_tlsfp_past_64_blocks(engine):
+    case, want = wide()
+    tc.assert_same(tc.run_device(engine, case), want, "wide")
